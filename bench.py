@@ -5,6 +5,8 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port 29511 \
            bench.py --gpus N --steps K --warmup W                      (N > 1: one rank per GPU)
     python bench.py --workload llama8b [--gpus N ...]                  (BASELINE.json configs[4]: strong scaling)
+    python bench.py --full [...]                                       (everything beside the headline, below)
+    python bench.py --dump-outputs DIR [...]                           (the last timed step's outputs as DIR/<name>.npy)
 
 Default workload.  One "step" = one pass of the decompress hot path over one batch: a 4 GiB synthetic bf16 tensor
 (N(0, 0.02) like model weights, generated on the device, 2 147 483 648 elements, 16 384 chunks of 256 KiB), compressed
@@ -16,9 +18,20 @@ Before the W warm-up steps the decode is launched `--settle-launches` times (def
 JSON line): after idle or other kernels the clocks need ~12 launches (25 ms) of this kernel to settle
 (profiles/r01z2_launch_time_ramp.txt); every timed step is a full step either way.
 
-Also on the JSON line:
+A plain run does only what the headline needs: set-up (the tensor, its body, one checked decode), the settle launches, the
+W warm-up steps, exactly K timed steps, the outputs when --dump-outputs is given, and the line (its `metric` keeps its
+words: the compress figures it names are on the --full line).  On it beside `value`:
+  ms_per_step        wall milliseconds of one timed step (K steps between two device-wide synchronisations, / K)
   roofline           decompress: (N + C_payload) bytes / avg launch time over the K timed steps, measured with HIP events on
                      the launch stream, vs the 8 TB/s HBM3E peak
+  rccl_ranks         ranks that took part in an all_reduce over RCCL (N > 1 or under torch.distributed.run)
+
+--dump-outputs DIR.  After the timed steps, what the last of them decoded, as float32 .npy files (about 25 MB in all): the
+bf16 values at 4 Mi fixed, seeded element positions, the first and the last 1 Mi elements, and (float64) the byte sum of every
+256 KiB chunk.  The inputs are seeded, so two builds run with the same arguments can be compared file for file.  With
+--workload llama8b: the values at up to 8 Ki fixed positions of every tensor, one file per dtype.
+
+--full adds everything else the benchmark measures or checks (each leg outside every timed region of the headline):
   compress_*         the same tensor compressed K/2 times into a body buffer allocated ONCE outside the loop, every step
                      timed with HIP events (avg / min / median); compress_roofline prices (N + C_payload) on the avg
   other_dtypes       fp16 / fp32 / fp8-e4m3 tensors of 1 GiB each (BASELINE.json configs[2]): event-timed decode and
@@ -36,12 +49,13 @@ Also on the JSON line:
   llama8b            BASELINE.json configs[4] on the same line at every N: the --workload llama8b run (strong scaling: the
                      chunk ranges of every tensor split over the ranks), value / ms / (N + C)/t fraction, and at N = 1 a sample
                      of its batched bodies compared with the CPU oracle's
-  rccl_ranks         ranks that took part in an all_reduce over RCCL (N > 1 or under torch.distributed.run)
+  device_under_load  shader clock / power of the busy GPU; kernels.compress; at N = 1 on a box with several GPUs, multi_dev_inprocess
 
 --workload llama8b.  The 291 tensors of a Llama-3-8B checkpoint (bf16, N(0, 0.02), ~16 GB) plus an fp8-e4m3 copy of
 its linear weights (~7 GB), synthesised on the devices.  Every tensor's chunks are split into WORLD_SIZE contiguous
 ranges (zipnn_amd.sharding.chunk_ranges); rank g codes range g of every tensor with one batched call per direction.
-The total work is fixed, so the line says "scaling": "strong"; at N = 1 the whole model runs on one GPU.
+The total work is fixed, so the line says "scaling": "strong"; at N = 1 the whole model runs on one GPU.  Its compress
+timing and (N = 1) the comparison of its bodies with the CPU oracle's are --full legs.
 """
 import argparse
 import json
@@ -86,6 +100,62 @@ def time_events(fn, steps):
         ev[i + 1].record()
     torch.cuda.synchronize()
     return [ev[i].elapsed_time(ev[i + 1]) for i in range(steps)]
+
+
+DUMP_LIMIT = 64 << 20            # bytes of .npy payload one --dump-outputs may write
+
+
+def sample_positions(numel, k, seed):
+    """k fixed element positions in [0, numel), sorted (every position when numel <= k): the same for every run with the same seed."""
+    if numel <= k:
+        return torch.arange(numel, dtype=torch.int64)
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(0, numel, (k,), generator=g, dtype=torch.int64).sort().values
+
+
+def elements_as_float(buf, byte_pos, dtype):
+    """The `dtype` elements that start at the byte offsets `byte_pos` of the uint8 device tensor `buf`, as a float32 numpy array."""
+    es = torch.empty(0, dtype=dtype).element_size()
+    pos = byte_pos.to(buf.device)
+    idx = (pos[:, None] + torch.arange(es, device=buf.device)).reshape(-1)
+    return buf[idx].view(dtype).float().cpu().numpy()
+
+
+def dump_outputs(dirname, arrays):
+    """DIR/<name>.npy for every array (float32 / float64 only, DUMP_LIMIT bytes in all)."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"{total} bytes of outputs, more than {DUMP_LIMIT}"
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def headline_outputs(out, n_bytes):
+    """What the caller of the headline decode receives — the bf16 tensor in `out` — sampled: 4 Mi fixed positions, the first and the last
+    1 Mi elements (float32), and the byte sum of every 256 KiB chunk (float64: exact, every byte of the output is in one of them)."""
+    numel = n_bytes // 2
+    k = min(1 << 20, numel)
+    pos = sample_positions(numel, 1 << 22, 2024) * 2
+    return {"decompressed_bf16_sample": elements_as_float(out, pos, torch.bfloat16),
+            "decompressed_bf16_head": elements_as_float(out, torch.arange(k, dtype=torch.int64) * 2, torch.bfloat16),
+            "decompressed_bf16_tail": elements_as_float(out, torch.arange(numel - k, numel, dtype=torch.int64) * 2, torch.bfloat16),
+            "decompressed_chunk_byte_sums": torch.cat([s.view(-1, CHUNK).sum(dim=1, dtype=torch.int32)          # (256 MiB at a time: no 8-byte copy
+                                                       for s in out.split(1024 * CHUNK)]).double().cpu().numpy()}   #  of the whole output)
+
+
+def batch_outputs(outs, items):
+    """llama8b: the decoded tensors of the batch (uint8 views, bf16 or fp8 by their plane count), up to 8 Ki fixed positions of each,
+    concatenated in batch order, one float32 array per dtype."""
+    import numpy as np
+    f8 = getattr(torch, "float8_e4m3fn", None)
+    got = {}
+    for i, (o, it) in enumerate(zip(outs, items)):
+        dt, name = (torch.bfloat16, "llama8b_bf16_sample") if it[1] == 2 else (f8, "llama8b_fp8_sample")
+        es = torch.empty(0, dtype=dt).element_size()
+        got.setdefault(name, []).append(elements_as_float(o, sample_positions(o.numel() // es, 8192, 5000 + i) * es, dt))
+    return {k: np.concatenate(v) for k, v in got.items()}
 
 
 def device_state_under_load(burst):
@@ -648,7 +718,8 @@ def pin_rank_to_its_gpus_numa_node(dev_index):
         return {"pinned": False, "why": repr(e)[:120]}
 
 
-def run_llama8b(args, lib, codec, device, world, rank, dist, td, sample_oracle=False):
+def run_llama8b(args, lib, codec, device, world, rank, dist, td, sample_oracle=False, full=True, dump_dir=None):
+    """full: also time the batched compress; dump_dir: rank 0 writes the last timed step's outputs there (batch_outputs)."""
     from zipnn_amd import sharding
     shapes = llama8b_shapes(layers=args.layers)
     f8 = getattr(torch, "float8_e4m3fn", None)
@@ -696,16 +767,19 @@ def run_llama8b(args, lib, codec, device, world, rank, dist, td, sample_oracle=F
     dms = time_events(lambda: codec.decompress_device_batch(lib, ditems, check=False, into=into), args.steps)
     barrier()
     elapsed = time.perf_counter() - t0
-    csteps = max(1, args.steps // 2)
-    codec.compress_device_batch(lib, items)
-    encode_kernels = lib.last_kernels()
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(csteps):
-        codec.compress_device_batch(lib, items)
-    barrier()
-    c_elapsed = time.perf_counter() - t1
     exact = exact and all(bool(torch.equal(o, it[0])) for o, it in zip(outs, items))
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, batch_outputs(outs, items))
+    csteps, c_elapsed, encode_kernels = max(1, args.steps // 2), 0.0, None
+    if full:
+        codec.compress_device_batch(lib, items)
+        encode_kernels = lib.last_kernels()
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(csteps):
+            codec.compress_device_batch(lib, items)
+        barrier()
+        c_elapsed = time.perf_counter() - t1
     rank_ms = None
     if dist:
         rank_ms = rank_spread(td, device, elapsed / args.steps * 1e3, world)
@@ -728,11 +802,14 @@ def run_llama8b(args, lib, codec, device, world, rank, dist, td, sample_oracle=F
                                        f"{total_bytes / 1e9:.2f} GB in all; every tensor's chunks split into {world} contiguous ranges, one batched call per rank "
                                        "(BASELINE.json configs[4])",
                            "tensors_per_rank": len(items), "parallelism": f"chunk-range-sharded x{world}, no collectives"},
-                "compress_GBps": round(total_bytes * csteps / c_elapsed / 1e9, 2), "compress_ms_per_step": round(c_elapsed / csteps * 1e3, 3),
                 "ratio": round(c_bytes / total_bytes, 5), "bit_exact_roundtrip": exact,
                 "rank0_decode_ms": {k: round(v, 4) for k, v in d.items()}, "rank_ms_per_step": rank_ms,
                 "partition": llama8b_partition(world, args.layers), "partition_at_8_ranks": llama8b_partition(8, args.layers),
-                "kernels": {"decompress": decode_kernels, "compress": encode_kernels}}
+                "kernels": {"decompress": decode_kernels}}
+        if full:
+            line["compress_GBps"] = round(total_bytes * csteps / c_elapsed / 1e9, 2)
+            line["compress_ms_per_step"] = round(c_elapsed / csteps * 1e3, 3)
+            line["kernels"]["compress"] = encode_kernels
         if c_payload is not None:                     # (N + C) / t on rank 0's event-timed launches, as a fraction of 8 TB/s
             line["decompress_roofline_frac"] = round((total_bytes + c_payload) / (d["avg"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
         if world == 1 and sample_oracle:
@@ -760,6 +837,39 @@ def run_llama8b(args, lib, codec, device, world, rank, dist, td, sample_oracle=F
     return line
 
 
+def full_legs(args, line, lib, codec, device, world, rank, dist, td, n_bytes, body):
+    """--full: every leg beside the headline, added to rank 0's `line` (None on the other ranks), each outside every timed region of the headline.
+    The --no-* options leave legs out.  `body`: the headline tensor's compressed body (the CPU baseline compares against it)."""
+    # ---- BASELINE.json configs[4] on the same line, at every N (every rank takes part; strong scaling) ----
+    if not args.no_llama8b:
+        import copy
+        a2 = copy.copy(args); a2.steps = max(2, min(args.steps, 10)); a2.warmup = min(args.warmup, 3)
+        llama = run_llama8b(a2, lib, codec, device, world, rank, dist, td, sample_oracle=(world == 1))
+        torch.cuda.empty_cache()
+        if rank == 0:
+            line["llama8b"] = llama
+    if rank == 0:
+        if world == 1 and not args.no_other_dtypes:
+            line["other_dtypes"] = other_dtypes(lib, codec, device, max(4, min(args.steps, 20)), cpu_compare=not args.no_cpu_baseline)
+        if world == 1 and not args.no_other_dtypes:
+            line["sizes"] = size_sweep(lib, codec, device, max(4, min(args.steps, 20)))
+        if world == 1 and not args.no_plugin:
+            line["plugin_gpt2"] = plugin_gpt2(lib, device)
+        if world == 1 and not args.no_plugin:
+            line["host_path"] = host_path(lib, device)
+        if world == 1 and not args.no_cpu_baseline:
+            sample = min(args.cpu_sample_mib << 20, n_bytes) // CHUNK * CHUNK
+            if sample:
+                xs = make_tensor(sample, device, 1234 + 1000 * rank)       # (the same seeds: the first `sample` bytes of the timed tensor)
+                fs = codec.flat_bytes(xs)
+                sbody = body if sample == n_bytes else codec.compress_device(lib, fs, P, ROT, BMODE, CHUNK, THR)
+                line["cpu_baseline"] = cpu_baseline(fs.cpu().numpy(), sbody.cpu().numpy())
+                del xs, fs, sbody
+        if world == 1:                           # (last, and in a child process with a time limit: first contact with several devices in one process)
+            torch.cuda.empty_cache()
+            line["multi_dev_inprocess"] = multi_dev_isolated()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -779,7 +889,14 @@ def main():
     ap.add_argument("--no-llama8b", action="store_true", help="skip the llama8b sub-run on the default line (BASELINE.json configs[4])")
     ap.add_argument("--multi-dev-leg", action="store_true", help="(internal) run only the in-process multi-device leg and print its JSON: the child of multi_dev_isolated()")
     ap.add_argument("--cpu-sample-mib", type=int, default=4096, help="bytes of the tensor the CPU reference is timed on and the GPU frame is compared on")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (compress, device state, llama8b, other dtypes, sizes, plugin, host path, CPU baseline, "
+                         "multi-device); the --no-* options trim this set.  Off: set-up, warm-up, the timed steps, the outputs, the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one decoded as DIR/<name>.npy (float32 / float64, a fixed seeded sample, < 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.multi_dev_leg:                       # the child of multi_dev_isolated(): its own process, its own contexts on every device, one JSON value on stdout
         from zipnn_amd import _capi, codec
         print(json.dumps(multi_dev_inprocess(_capi.lib(), codec)), flush=True)
@@ -813,7 +930,7 @@ def main():
         rccl_ranks = int(ones.item())
 
     if args.workload == "llama8b":
-        line = run_llama8b(args, lib, codec, device, world, rank, dist, td, sample_oracle=(world == 1))
+        line = run_llama8b(args, lib, codec, device, world, rank, dist, td, sample_oracle=(world == 1 and args.full), full=args.full, dump_dir=args.dump_outputs)
         if rank == 0:
             line["rccl_ranks"] = rccl_ranks
             print(json.dumps(line), flush=True)
@@ -853,28 +970,34 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     d = stats(kernel_ms)
-    # the output of the LAST timed step, and one more call with the device-side status read back
+    # the output of the LAST timed step
     exact = exact and bool(torch.equal(out, flat))
-    out.zero_()
-    codec.decompress_device(lib, body, P, ROT, BMODE, CHUNK, n_bytes, out=out, check=True)
-    exact = exact and bool(torch.equal(out, flat))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, headline_outputs(out, n_bytes))
 
-    # ---- compress: same tensor, K/2 timed steps into the preallocated body buffer -------
-    for _ in range(max(2, min(args.warmup, 4))):
-        codec.compress_device(lib, flat, P, ROT, BMODE, CHUNK, THR, body=body_buf)
-    barrier()
-    t1 = time.perf_counter()
-    csteps = max(1, args.steps // 2)
-    used = [0]
+    c_elapsed, same_body = 0.0, True
+    if args.full:
+        # one more call with the device-side status read back
+        out.zero_()
+        codec.decompress_device(lib, body, P, ROT, BMODE, CHUNK, n_bytes, out=out, check=True)
+        exact = exact and bool(torch.equal(out, flat))
 
-    def one_compress():
-        used[0] = codec.compress_device(lib, flat, P, ROT, BMODE, CHUNK, THR, body=body_buf).numel()
-    comp_ms = time_events(one_compress, csteps)
-    barrier()
-    c_elapsed = time.perf_counter() - t1
-    c = stats(comp_ms)
-    same_body = used[0] == body.numel() and bool(torch.equal(body_buf[:used[0]], body))
-    encode_kernels = lib.last_kernels()
+        # ---- compress: same tensor, K/2 timed steps into the preallocated body buffer -------
+        for _ in range(max(2, min(args.warmup, 4))):
+            codec.compress_device(lib, flat, P, ROT, BMODE, CHUNK, THR, body=body_buf)
+        barrier()
+        t1 = time.perf_counter()
+        csteps = max(1, args.steps // 2)
+        used = [0]
+
+        def one_compress():
+            used[0] = codec.compress_device(lib, flat, P, ROT, BMODE, CHUNK, THR, body=body_buf).numel()
+        comp_ms = time_events(one_compress, csteps)
+        barrier()
+        c_elapsed = time.perf_counter() - t1
+        c = stats(comp_ms)
+        same_body = used[0] == body.numel() and bool(torch.equal(body_buf[:used[0]], body))
+        encode_kernels = lib.last_kernels()
 
     rank_ms = None
     if dist:
@@ -884,13 +1007,12 @@ def main():
         elapsed, c_elapsed, bad = tt.tolist()
         exact = exact and bad == 0.0
 
+    line = None
     if rank == 0:
         total_bytes = n_bytes * world
         value = total_bytes * args.steps / elapsed / 1e9
-        cvalue = total_bytes * csteps / c_elapsed / 1e9
         alg = n_bytes + c_payload
         achieved = alg / (d["avg"] * 1e-3) / 1e9
-        c_achieved = alg / (c["avg"] * 1e-3) / 1e9
         traffic, traffic_src = traffic_of("bf16", n_bytes)
         line = {
             "metric": "bf16 decompress GB/s (uncompressed bytes / s; compress GB/s beside it)",
@@ -901,58 +1023,38 @@ def main():
             "config": {"workload": f"{n_bytes / (1 << 30):g} GiB synthetic bf16 N(0,0.02) tensor per GPU, 256 KiB chunks, "
                                    "byte-split + huff0 (BASELINE.json configs[1])",
                        "chunks_per_gpu": n_bytes // CHUNK, "parallelism": f"chunk-sharded x{world}, no collectives"},
-            "compress_GBps": round(cvalue, 2), "compress_ms_per_step": round(c_elapsed / csteps * 1e3, 3),
-            "compress_steps": csteps, "compress_frame_identical_every_step": same_body,
             "ratio": round((body.numel() + 32) / n_bytes, 5), "bit_exact_roundtrip": exact,
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_src,
                          "kernel": decode_kernels, "avg_launch_ms": round(d["avg"], 4),
                          "min_launch_ms": round(d["min"], 4), "median_launch_ms": round(d["median"], 4),
                          "algorithmic_bytes": alg},
-            "compress_roofline": {"bound": "hbm", "achieved": round(c_achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                                  "frac": round(c_achieved / HBM_PEAK_GBPS, 4), "kernel": encode_kernels,
-                                  "avg_call_ms": round(c["avg"], 4), "min_call_ms": round(c["min"], 4), "median_call_ms": round(c["median"], 4),
-                                  "algorithmic_bytes": alg,
-                                  "note": "events bracket the whole zn_compress_dev call — the one-pass encoder + the size scan for a bf16 call of this size (zn_k_encode_onepass: N + C over HBM, the chunk's second read aimed at the Infinity Cache), the four-kernel encoder (2 N + C) otherwise: see `kernel` — + one read-back of length and status"},
-            "kernels": {"decompress": decode_kernels, "compress": encode_kernels},
+            "kernels": {"decompress": decode_kernels},
         }
+        if args.full:
+            cvalue = total_bytes * csteps / c_elapsed / 1e9
+            c_achieved = alg / (c["avg"] * 1e-3) / 1e9
+            line.update({
+                "compress_GBps": round(cvalue, 2), "compress_ms_per_step": round(c_elapsed / csteps * 1e3, 3),
+                "compress_steps": csteps, "compress_frame_identical_every_step": same_body,
+                "compress_roofline": {"bound": "hbm", "achieved": round(c_achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                                      "frac": round(c_achieved / HBM_PEAK_GBPS, 4), "kernel": encode_kernels,
+                                      "avg_call_ms": round(c["avg"], 4), "min_call_ms": round(c["min"], 4), "median_call_ms": round(c["median"], 4),
+                                      "algorithmic_bytes": alg,
+                                      "note": "events bracket the whole zn_compress_dev call — the one-pass encoder + the size scan for a bf16 call of this size (zn_k_encode_onepass: N + C over HBM, the chunk's second read aimed at the Infinity Cache), the four-kernel encoder (2 N + C) otherwise: see `kernel` — + one read-back of length and status"}})
+            line["kernels"]["compress"] = encode_kernels
         if share:
             line["dry_run_shared_gpu"] = True
-        line["device_under_load"] = device_state_under_load(lambda: [codec.decompress_device(lib, body, P, ROT, BMODE, CHUNK, n_bytes, out=out, check=False) for _ in range(120)])
+        if args.full:
+            line["device_under_load"] = device_state_under_load(lambda: [codec.decompress_device(lib, body, P, ROT, BMODE, CHUNK, n_bytes, out=out, check=False) for _ in range(120)])
         line["rccl_ranks"] = rccl_ranks
         line["rank0_cpu_affinity"] = affinity
         line["rank_ms_per_step"] = rank_ms          # every rank's own wall time per step (a straggler shows as max >> min); null without torch.distributed
-    # ---- BASELINE.json configs[4] on the same line, at every N (every rank takes part; strong scaling) ----
-    del x, flat, body_buf, out
-    torch.cuda.empty_cache()
-    if not args.no_llama8b:
-        import copy
-        a2 = copy.copy(args); a2.steps = max(2, min(args.steps, 10)); a2.warmup = min(args.warmup, 3)
-        llama = run_llama8b(a2, lib, codec, device, world, rank, dist, td, sample_oracle=(world == 1))
+    if args.full:
+        del x, flat, body_buf, out
         torch.cuda.empty_cache()
-        if rank == 0:
-            line["llama8b"] = llama
+        full_legs(args, line, lib, codec, device, world, rank, dist, td, n_bytes, body)
     if rank == 0:
-        if world == 1 and not args.no_other_dtypes:
-            line["other_dtypes"] = other_dtypes(lib, codec, device, max(4, min(args.steps, 20)), cpu_compare=not args.no_cpu_baseline)
-        if world == 1 and not args.no_other_dtypes:
-            line["sizes"] = size_sweep(lib, codec, device, max(4, min(args.steps, 20)))
-        if world == 1 and not args.no_plugin:
-            line["plugin_gpt2"] = plugin_gpt2(lib, device)
-        if world == 1 and not args.no_plugin:
-            line["host_path"] = host_path(lib, device)
-        if world == 1 and not args.no_cpu_baseline:
-            sample = min(args.cpu_sample_mib << 20, n_bytes) // CHUNK * CHUNK
-            if sample:
-                xs = make_tensor(sample, device, 1234 + 1000 * rank)       # (the same seeds: the first `sample` bytes of the timed tensor)
-                fs = codec.flat_bytes(xs)
-                sbody = body if sample == n_bytes else codec.compress_device(lib, fs, P, ROT, BMODE, CHUNK, THR)
-                line["cpu_baseline"] = cpu_baseline(fs.cpu().numpy(), sbody.cpu().numpy())
-                del xs, fs, sbody
-        if world == 1:                           # (last, and in a child process with a time limit: first contact with several devices in one process)
-            del body
-            torch.cuda.empty_cache()
-            line["multi_dev_inprocess"] = multi_dev_isolated()
         print(json.dumps(line), flush=True)
     if dist:
         td.barrier()

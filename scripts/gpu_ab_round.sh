@@ -25,10 +25,10 @@ PY
 )
 echo "picked: $PICK" | tee "$OUT/picked.txt"
 if [ "$PICK" != "new" ]; then cp "zipnn_amd/libzipnn_hip_ab_$PICK.so" zipnn_amd/libzipnn_hip.so; fi
-echo "== bench =="; timeout 300 python bench.py --steps 20 --warmup 2 2>"$OUT/bench.err" | tail -1 | tee "$OUT/bench.json"
+echo "== bench =="; timeout 300 python bench.py --full --steps 20 --warmup 2 2>"$OUT/bench.err" | tail -1 | tee "$OUT/bench.json"
 echo "== rocprofv3 kernel stats =="
 cd /tmp && export TMPDIR=/tmp
-timeout 240 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o bench -- python "$R/bench.py" --steps 20 --warmup 2 --no-cpu-baseline > "$OUT/rocprof.log" 2>&1
+timeout 240 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o bench -- python "$R/bench.py" --full --steps 20 --warmup 2 --no-cpu-baseline > "$OUT/rocprof.log" 2>&1
 tail -2 "$OUT/rocprof.log"
 find "$OUT/prof" -name '*kernel_stats*' | head -1 | while read f; do cp "$f" "$OUT/kernel_stats.csv"; head -8 "$f"; done
 find "$OUT/prof" -name '*kernel_trace*' -size +20M -delete 2>/dev/null

@@ -17,13 +17,13 @@ if [ "$(python -c 'import torch; print(torch.cuda.device_count())')" -lt "$N" ];
   export ZN_BENCH_SHARE_GPU=1 ZN_BENCH_BACKEND=gloo
 fi
 echo "== bench.py, $N ranks, 0.25 GiB per rank =="
-timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus "$N" --gib 0.25 --steps 10 --warmup 5 \
+timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus "$N" --gib 0.25 --steps 10 --warmup 5 --full \
   --no-cpu-baseline --no-other-dtypes --no-plugin --layers 2 2>/dev/null | grep "^{" | python -c "
 import json, sys
 j = json.loads(sys.stdin.readline())
 print('n_gpus', j['n_gpus'], 'rccl_ranks', j['rccl_ranks'], 'value', j['value'], 'GB/s', 'rank_ms', j.get('rank_ms_per_step'), 'exact', j['bit_exact_roundtrip'])
 print('llama8b', j['llama8b']['value'], 'GB/s', 'rank_ms', j['llama8b'].get('rank_ms_per_step'), 'exact', j['llama8b']['bit_exact_roundtrip'])"
 echo "== bench.py, one process, every visible GPU through zn_decompress_multi_dev =="
-timeout 300 python bench.py --gib 0.25 --steps 5 --warmup 2 --no-cpu-baseline --no-other-dtypes --no-plugin --no-llama8b 2>/dev/null | grep "^{" | python -c "
+timeout 300 python bench.py --gib 0.25 --steps 5 --warmup 2 --full --no-cpu-baseline --no-other-dtypes --no-plugin --no-llama8b 2>/dev/null | grep "^{" | python -c "
 import json, sys
 print('multi_dev_inprocess', json.loads(sys.stdin.readline()).get('multi_dev_inprocess'))"

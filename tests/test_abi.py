@@ -108,3 +108,33 @@ def test_bench_runs_its_multi_device_leg_in_a_child_process_with_a_time_limit(mo
     assert bench.multi_dev_isolated(timeout_s=600) is None         # the child (a real second process: it sees this machine's devices) prints null
     r = bench.multi_dev_isolated(timeout_s=0.05)
     assert r["devices"] == 2 and "timed out" in r["error"]
+
+
+def test_bench_dump_outputs_sample_what_the_decode_returned(tmp_path):
+    """bench.py --dump-outputs: the files hold the decoded tensor's own values (a fixed, seeded sample, the head, the tail, every chunk's byte
+    sum), as float32 / float64 and within the size limit; the same seed picks the same positions.  Here on a CPU tensor standing in for `out`."""
+    import sys
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 8 * bench.CHUNK
+    x = (torch.randn(n // 2, generator=torch.Generator().manual_seed(7)) * 0.02).to(torch.bfloat16)
+    out = x.view(torch.uint8)
+    got = bench.headline_outputs(out, n)
+    xf = x.float().numpy()
+    assert np.array_equal(got["decompressed_bf16_sample"], xf[bench.sample_positions(n // 2, 1 << 22, 2024).numpy()])
+    assert np.array_equal(got["decompressed_bf16_head"], xf[:1 << 20]) and np.array_equal(got["decompressed_bf16_tail"], xf[-(1 << 20):])
+    assert np.array_equal(got["decompressed_chunk_byte_sums"], out.numpy().reshape(-1, bench.CHUNK).sum(1).astype(np.float64))
+    big = bench.sample_positions(1 << 31, 1 << 22, 2024)
+    assert torch.equal(big, bench.sample_positions(1 << 31, 1 << 22, 2024)) and int(big.max()) < (1 << 31)
+    f8 = torch.float8_e4m3fn
+    y = (torch.randn(5000, generator=torch.Generator().manual_seed(8)) * 0.02).to(f8)
+    into = torch.cat([out[:6000], y.view(torch.uint8)])
+    b = bench.batch_outputs([into[:6000], into[6000:]], [(None, 2), (None, 1)])
+    assert np.array_equal(b["llama8b_bf16_sample"], xf[:3000]) and np.array_equal(b["llama8b_fp8_sample"], y.float().numpy())
+    bench.dump_outputs(str(tmp_path), got)
+    assert sorted(os.listdir(tmp_path)) == sorted(k + ".npy" for k in got)
+    assert np.array_equal(np.load(tmp_path / "decompressed_bf16_sample.npy"), got["decompressed_bf16_sample"])
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "big"), {"a": np.zeros(bench.DUMP_LIMIT // 4 + 1, dtype=np.float32)})

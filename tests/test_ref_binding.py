@@ -52,12 +52,22 @@ def test_the_reference_s_own_stress_test_passes_on_this_library(simt_lib, tmp_pa
     fp8), run by pytest in a subprocess with tests/ref_binding/ ahead of the reference on sys.path: the stock Python package, its
     own assertions, this library underneath (emulated kernels here).  Runs in a scratch directory — the test writes its
     temporary safetensors files into the cwd — and writes nothing under /root/reference (no bytecode, no pytest cache)."""
+    import shutil
+    # (the stress test writes a scratch file next to itself and imports ../scripts: it runs from a copy of both in the scratch
+    #  directory, so that the read-only reference tree is only read)
+    work = tmp_path / "ref"
+    for sub in ("tests", "scripts"):
+        (work / sub).mkdir(parents=True)
+        for f in os.listdir(os.path.join(REF, sub)):
+            if os.path.isfile(os.path.join(REF, sub, f)):
+                shutil.copyfile(os.path.join(REF, sub, f), work / sub / f)      # (contents only: the copies are writable)
     env = dict(os.environ)
     env["PYTHONPATH"] = os.pathsep.join([os.path.join(ROOT, "tests", "ref_binding"), REF])
     env["PYTHONDONTWRITEBYTECODE"] = "1"
     env["ZIPNN_HIP_LIB"] = simt_lib.path
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(REF, "tests", "simple_stress_tests.py"), "-x", "-q", "-p", "no:cacheprovider",
+    r = subprocess.run([sys.executable, "-m", "pytest", str(work / "tests" / "simple_stress_tests.py"), "-x", "-q", "-p", "no:cacheprovider",
                         "--rootdir", str(tmp_path)], env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert " passed" in r.stdout and "failed" not in r.stdout
     assert not os.path.isdir(os.path.join(REF, "zipnn", "__pycache__"))
+    assert sorted(os.listdir(os.path.join(REF, "tests"))) == sorted(os.listdir(work / "tests"))      # nothing left behind in the reference tree
