@@ -1136,3 +1136,100 @@ def test_mixed_batch_of_two_full_kinds_takes_the_two_stream_path(simt_lib):
     for d, o in zip(datas[1:], outs):
         assert o.numpy().tobytes() == d
     assert "(two streams)" not in simt_lib.last_kernels()
+
+
+# ---------------------------------------------------------------------------------------
+# Batches of checkpoint scale (tests/test_gpu_batch_scale.py runs them on hardware): hundreds to thousands of small tensors, most of them ragged
+# ---------------------------------------------------------------------------------------
+_RAGGED_KINDS = {2: [("bf16", 1), ("fp16", 0), ("rand", 1), ("const", 1), ("skew", 0), ("bf16", 1), ("fp16", 0)],
+                 1: [("fp8", 0), ("rand", 0), ("const", 0), ("skew", 0)], 4: [("fp32", 1), ("rand", 1), ("skew", 0)]}
+
+
+def _ragged_batch(n2, seed, chunk=8192, n1=0, n4=0, full_max=3, whole_every=17, kinds=None, tail_max=None, full_min=0):
+    """Specs (kind, nb, P, rot, bm, chunk) + data of a batch with EXACTLY n2 / n1 / n4 two- / one- / four-plane tensors that end in a partial chunk:
+    full_min .. full_max full chunks + a tail; tails whose planes are just below / at / just above ZN_TAIL_WG_MIN_PLANE (512 bytes) or of any length; raw (rand),
+    RLE (const), one- and two-Huffman-plane (skew, rotate 0) and weight-like distributions.  Every `whole_every`-th entry is a whole-chunk or an empty tensor
+    of some plane count, placed between the ragged ones.  Deterministic in `seed`."""
+    r = np.random.default_rng(seed)
+    kinds = kinds or _RAGGED_KINDS
+    ragged = []
+    for P, n in ((2, n2), (1, n1), (4, n4)):
+        ks = kinds.get(P)
+        for i in range(n):
+            kind, rot = ks[i % len(ks)]
+            full = full_min + i % (full_max - full_min + 1)
+            near = [P * 511, P * 512 - 1, P * 512, P * 512 + 1, P * 513]      # planes of 511 / 512 / 513 bytes (zo_plane_lens: the first planes get the odd bytes)
+            tail = near[(i // len(ks)) % len(near)] if r.random() < 0.4 else int(r.integers(1, tail_max or chunk))
+            tail = min(tail, chunk - 1)
+            ragged.append((kind, full * chunk + tail, P, rot, 220 if P == 4 else 10, chunk))
+    order = r.permutation(len(ragged))
+    specs = []
+    for j, i in enumerate(order):
+        specs.append(ragged[i])
+        if whole_every and j % whole_every == whole_every - 1:
+            Ps = [P for P, n in ((1, n1), (2, n2), (4, n4)) if n]
+            P = Ps[(j // whole_every) % len(Ps)]
+            kind = {1: "fp8", 2: "bf16", 4: "fp32"}[P]
+            specs.append((kind, (j // whole_every // len(Ps)) % 3 * chunk, P, 0 if P == 1 else 1, 220 if P == 4 else 10, chunk))    # (one in three empty)
+    datas = []
+    for i, (kind, nb, P, rot, bm, ch) in enumerate(specs):
+        d = _gen2(kind, nb, seed * 100003 + i)
+        assert len(d) == nb
+        datas.append(d)
+    return specs, datas
+
+
+def _oracle_bodies(specs, datas, threads=1):
+    return [O.compress_frame(HDR, d, P, rot, bm, chunk, threads=threads)[32:] for (kind, nb, P, rot, bm, chunk), d in zip(specs, datas)]
+
+
+def _tail_planes_expected(specs, bodies):
+    """The planes of partial last chunks the tail workgroups take (zn_decode_fused.hip, zn_decode_tail_wg's entry condition): Huffman-typed, more than one
+    byte (not RLE), 512 bytes <= plane <= 128 KiB — read from the frames' type bytes and cumSizes, plane lengths by the split rule (oracle zo_plane_lens)."""
+    n = 0
+    for (kind, nb, P, rot, bm, chunk), body in zip(specs, bodies):
+        if nb == 0 or nb % chunk == 0:
+            continue
+        K = -(-nb // chunk)
+        b = np.frombuffer(body, dtype=np.uint8)
+        types = b[:P * K].reshape(P, K)
+        cum = b[P * K: 9 * P * K].view(np.uint64).reshape(P, K)
+        t = nb - (K - 1) * chunk
+        for p in range(P):
+            plen = t // P + (1 if p < t % P else 0)
+            cs = int(cum[p, K - 1]) - (int(cum[p, K - 2]) if K > 1 else 0)
+            n += int(types[p, K - 1] == 1 and cs > 1 and 512 <= plen <= 128 * 1024)
+    return n
+
+
+def _ragged_count(specs, P):
+    return sum(1 for s in specs if s[2] == P and s[1] % s[5])
+
+
+def _u8(b):
+    """bytes -> uint8 CPU tensor (an empty one for b"")."""
+    return torch.frombuffer(bytearray(b), dtype=torch.uint8) if len(b) else torch.empty(0, dtype=torch.uint8)
+
+
+def test_batch_of_129_ragged_tensors_splits_each_merge_over_16_workgroups(simt_lib, request):
+    """129 two-plane tensors with a partial last chunk in one batched call: zn_launch_decode_fused halves merge_per while merge_per * ntt > 4096, so each
+    tensor's partial chunk is merged by 16 workgroups (sub = jm of nsub = 16) — below 129 ragged tensors every call had 32.  One- and four-plane tensors ride
+    in launches of their own with other counts; whole-chunk and empty tensors sit between the ragged ones in the segment tables (the tail-slot search).
+    Decoded bytes == the sources, the tail workgroups took every plane the oracle's frames give them; then the same batch through the batched encoder,
+    every body == the oracle's (partial chunks as `ptails` of the fused launches)."""
+    from zipnn_amd import codec
+    request.addfinalizer(lambda: simt_lib.set_decode_wide(1))
+    simt_lib.set_decode_wide(0)                  # (pinned: the emulated device has one CU, automatic mode would pick the fused kernel anyway)
+    specs, datas = _ragged_batch(129, 5, chunk=4096, n1=3, n4=3, full_max=1, whole_every=40, tail_max=1200)
+    assert _ragged_count(specs, 2) == 129
+    bodies = _oracle_bodies(specs, datas)
+    outs = codec.decompress_device_batch(simt_lib, [(_u8(b), P, rot, bm, ch, nb) for b, (k, nb, P, rot, bm, ch) in zip(bodies, specs)])
+    assert simt_lib.last_kernels() == ";".join(["zn_k_decode_fused^rest+tail+merge"] * 3)
+    assert simt_lib.last_tail_planes() == _tail_planes_expected(specs, bodies) > 30
+    for i, (o, d) in enumerate(zip(outs, datas)):
+        assert o.numpy().tobytes() == d, (i, specs[i])
+    got = codec.compress_device_batch(simt_lib, [(_u8(d), P, rot, bm, ch, 0.95) for d, (k, nb, P, rot, bm, ch) in zip(datas, specs)])
+    assert "zn_k_encode_emit+tail" in simt_lib.last_kernels()
+    for i, (g, b) in enumerate(zip(got, bodies)):
+        assert g.numpy().tobytes() == b, (i, specs[i])
+
