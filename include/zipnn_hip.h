@@ -128,6 +128,35 @@ typedef struct zn_batch_item {
 } zn_batch_item;
 int zn_decompress_batch_dev(const zn_batch_item* items, size_t count, void* stream, int check);
 
+/* Chunk windows of device-resident bodies: item i decodes chunks [chunk_lo, chunk_hi) of its tensor from the WHOLE frame
+ * body where it lies — the kernels read the window's rows of the body's size tables themselves, so nothing is copied or
+ * re-based and the host never looks at the body.  For a checkpoint kept compressed in HBM: a layer, a tensor or a row
+ * range is decoded when it is needed.  A window [0, zn_num_chunks(orig_size, chunk)) is zn_decompress_batch_dev's item;
+ * chunk_lo == chunk_hi is an empty item; chunk_lo > chunk_hi or chunk_hi past the last chunk is ZN_E_ARG.  Everything
+ * else (stream, check, zn_decode_status) as for zn_decompress_batch_dev. */
+typedef struct zn_window_item {
+  const void* d_body; size_t body_len;      /* the WHOLE frame body, on the current device */
+  size_t orig_size;                         /* of the whole tensor */
+  size_t chunk_lo, chunk_hi;                /* decode chunks [chunk_lo, chunk_hi) */
+  void* d_dst;                              /* receives min(chunk_hi*chunk, orig_size) - chunk_lo*chunk bytes */
+  int num_buf, bits_mode, bytes_mode; size_t chunk;
+  const void* d_delta;                      /* NULL, or the whole tensor's base (orig_size bytes); the library offsets it */
+} zn_window_item;
+int zn_decompress_window_batch_dev(const zn_window_item* items, size_t count, void* stream, int check);
+
+/* A prepared batched decode.  zn_plan_create (on the current device) does everything a batched decode call does before
+ * its first launch — argument and geometry checks, the choice of kernels (the tuning knobs are read here, once), the
+ * segment table — and keeps the table in device memory the plan owns.  zn_plan_run reserves the shared workspace, takes
+ * a status slot and launches: no host-to-device copy and no host-side wait for earlier device work, so a caller can
+ * enqueue the decode of layer i + 1 while layer i still runs.  It orders itself against other calls on the device as
+ * every decode call does; check = 0 with zn_decode_status works as usual.  The plan refers to the items' bodies,
+ * destinations and delta bases by address and does not own them: they must stay valid for every run.
+ * zn_plan_destroy waits for the plan's last run (an event recorded behind every run: that stream, not the whole device) before it frees the table.  zn_release_workspace leaves plans intact. */
+typedef struct zn_plan zn_plan;
+int zn_plan_create(const zn_window_item* items, size_t count, zn_plan** plan);
+int zn_plan_run(zn_plan* plan, void* stream, int check);
+int zn_plan_destroy(zn_plan* plan);
+
 /* Delta ("byte"/"file" delta_compressed_type of the reference, zipnn/zipnn.py:625-640 and :983-1004: the bytes
  * are XORed with a second buffer of the same length before compression and after decompression).  The XOR is
  * fused into the kernels that read the tensor / write the output — no extra pass over HBM.  d_delta = NULL gives

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Developer tool (GPU box): time the decode of prebuilt library variants against each other, interleaved
-(A B A B ...) so that clock drift hits both.  Usage: python scripts/ab_libs.py libA.so libB.so ...
+(A B A B ...) so that clock drift hits both.  Usage: python scripts/ab_libs.py [--small] [--rounds N] libA.so libB.so ...
+(--small: the 64 MiB and the ragged 100 MiB + 250 000 B bf16 tensors of bench.py's size sweep instead of the large cases; --rounds: interleaved rounds, best of all)
 (the variants are built here, in the container, e.g. from `git archive <commit> zipnn_amd/csrc`)."""
 import ctypes, os, sys, time
 import torch
@@ -16,10 +17,15 @@ def load(path):
 
 
 def main():
-    paths = sys.argv[1:]
+    argv = sys.argv[1:]
+    small = "--small" in argv
+    rounds = int(argv[argv.index("--rounds") + 1]) if "--rounds" in argv else 4
+    paths = [a for i, a in enumerate(argv) if not a.startswith("--") and (i == 0 or argv[i - 1] != "--rounds")]
     libs = [(os.path.basename(p), load(p)) for p in paths]
     C0 = 262144
     cases = [("bf16 4GiB", 4 << 30, 2, 1, 10, torch.bfloat16), ("fp32 1GiB", 1 << 30, 4, 1, 220, torch.float32), ("fp16 1GiB", 1 << 30, 2, 0, 10, torch.float16), ("fp8 1GiB", 1 << 30, 1, 0, 10, torch.float8_e4m3fn)]
+    if small:
+        cases = [("bf16 64MiB", 64 << 20, 2, 1, 10, torch.bfloat16), ("bf16 100MiB+250000", (100 << 20) + 250000, 2, 1, 10, torch.bfloat16)]
     st = torch.cuda.current_stream().cuda_stream
     for name, n, P, rot, bm, dt in cases:
         C = C0 if P > 1 else 131072
@@ -40,18 +46,19 @@ def main():
             assert L.zn_decompress_dev(body.data_ptr(), ln.value, P, rot, bm, C, n, out.data_ptr(), st, 1) == 0
             ok_ = torch.equal(out, flat); print("   roundtrip", k, ok_)
         body2 = torch.empty(cap, dtype=torch.uint8, device="cuda"); ln2 = ctypes.c_size_t(0)
-        for rnd in range(4):
+        reps = 10 if n >= (1 << 30) else 200
+        for rnd in range(rounds):
             for k, L in libs:
                 torch.cuda.synchronize(); t0 = time.perf_counter()
-                for _ in range(10):
+                for _ in range(reps):
                     L.zn_decompress_dev(body.data_ptr(), ln.value, P, rot, bm, C, n, out.data_ptr(), st, 0)
-                torch.cuda.synchronize(); best[k] = min(best[k], (time.perf_counter() - t0) / 10)
+                torch.cuda.synchronize(); best[k] = min(best[k], (time.perf_counter() - t0) / reps)
                 t0 = time.perf_counter()
                 for _ in range(4):
                     L.zn_compress_dev(flat.data_ptr(), n, P, rot, bm, C, 0.95, body2.data_ptr(), cap, ctypes.byref(ln2), st)
                 torch.cuda.synchronize(); bestc[k] = min(bestc[k], (time.perf_counter() - t0) / 4)
         for k, _ in libs:
-            print(f"{name:10s} {k:34s} decode {best[k] * 1e3:.3f} ms {n / best[k] / 1e9:6.0f} GB/s   compress {bestc[k] * 1e3:.3f} ms {n / bestc[k] / 1e9:6.0f} GB/s", flush=True)
+            print(f"{name:10s} {k:34s} decode {best[k] * 1e3:.4f} ms {n / best[k] / 1e9:6.0f} GB/s   compress {bestc[k] * 1e3:.3f} ms {n / bestc[k] / 1e9:6.0f} GB/s", flush=True)
         del x, flat, body, out, body2
 
 

@@ -1,0 +1,223 @@
+#!/usr/bin/env python
+"""Probe (GPU box): what a checkpoint that stays compressed in HBM costs and saves (zipnn_amd.ResidentCheckpoint).
+
+Llama-3-8B block shapes (bench.llama8b_shapes, as bench.py's `llama8b` workload), seeded N(0, 0.02) bf16 tensors, compressed by this library.
+Everything timed is checked against the source bytes.  Legs:
+  a  resident bytes against original bytes
+  b  per-block plan.run time, by device events
+  c  a window of k chunks of a large tensor against a whole tensor of k chunks, k = 64, 1 024, 4 096
+  d  host time to ENQUEUE a block while an earlier decode is still running: plan.run against zn_decompress_batch_dev
+  e  a full forward of a stack of torch.nn.Linear blocks with hook(), against the same stack with plain parameters
+Each leg runs in a child process under a time limit of its own; a leg that fails or runs out of time ends the probe.
+    python scripts/bench_resident.py [--layers 4] [--out profiles/resident_decode]
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+LEG_SECONDS = {"a": 240, "b": 240, "c": 300, "d": 240, "e": 300}
+CH = 256 * 1024
+
+
+def _blocks(layers, seed=7):
+    """-> (state dict of `layers` Llama-3-8B blocks on the device, [names of block i])"""
+    import torch
+    import bench
+    g = torch.Generator(device="cuda"); g.manual_seed(seed)
+    sd, per = {}, [[] for _ in range(layers)]
+    for name, shape, _linear in bench.llama8b_shapes(layers=layers):
+        if not name.startswith("model.layers."):
+            continue
+        sd[name] = (torch.randn(shape, generator=g, device="cuda") * 0.02).to(torch.bfloat16)
+        per[int(name.split(".")[2])].append(name)
+    return sd, per
+
+
+def _same(a, b):
+    import torch
+    return torch.equal(a.reshape(-1).view(torch.uint8), b.reshape(-1).view(torch.uint8))
+
+
+def _events_ms(fn, reps, warm=3):
+    import torch
+    for _ in range(warm):
+        fn()
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); fn(); e1.record(); e1.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return {"median_ms": statistics.median(out), "min_ms": min(out), "reps": reps}
+
+
+def leg_a(args):
+    from zipnn_amd import ResidentCheckpoint
+    sd, per = _blocks(args.layers)
+    store = ResidentCheckpoint.from_state_dict(sd, "cuda:0")
+    for k, v in sd.items():
+        assert _same(store.get_tensor(k), v), k
+    return {"layers": args.layers, "tensors": len(sd), "original_bytes": store.nbytes, "resident_bytes": store.resident_bytes,
+            "ratio": store.resident_bytes / store.nbytes}
+
+
+def leg_b(args):
+    import torch
+    from zipnn_amd import ResidentCheckpoint
+    sd, per = _blocks(args.layers)
+    store = ResidentCheckpoint.from_state_dict(sd, "cuda:0")
+    scratch = torch.empty(max(store.scratch_bytes(n) for n in per), dtype=torch.uint8, device="cuda")
+    res = []
+    for i, names in enumerate(per):
+        plan = store.plan(names, into=scratch)
+        t = _events_ms(plan.run, args.reps)
+        plan.status()
+        for k in names:
+            assert _same(plan.tensors[k], sd[k]), k
+        nbytes = sum(store.info(k)["nbytes"] for k in names)
+        t.update(block=i, bytes=nbytes, gb_per_s=nbytes / t["median_ms"] / 1e6)
+        res.append(t)
+        plan.close()
+    return {"blocks": res}
+
+
+def leg_c(args):
+    import torch
+    from zipnn_amd import _capi, codec
+    lib = _capi.lib()
+    g = torch.Generator(device="cuda"); g.manual_seed(11)
+    K_BIG = 8192
+    big = (torch.randn(K_BIG * CH // 2, generator=g, device="cuda") * 0.02).to(torch.bfloat16).view(torch.uint8)
+    body_big = codec.compress_device(lib, big, 2, 1, 10, CH, 0.95).clone()
+    st = torch.cuda.current_stream().cuda_stream
+    res = []
+    for k in (64, 1024, 4096):
+        lo = (K_BIG - k) // 2
+        whole_src = big[lo * CH:(lo + k) * CH]
+        body_k = codec.compress_device(lib, whole_src, 2, 1, 10, CH, 0.95).clone()
+        out = torch.empty(k * CH, dtype=torch.uint8, device="cuda")
+        win = [(body_big.data_ptr(), body_big.numel(), 2, 1, 10, CH, big.numel(), lo, lo + k, out.data_ptr())]
+        whole = [(body_k.data_ptr(), body_k.numel(), 2, 1, 10, CH, k * CH, 0, k, out.data_ptr())]
+        r = {"chunks": k}
+        for name, items in (("window", win), ("whole", whole), ("window_again", win), ("whole_again", whole)):      # interleaved: A B A B
+            out.zero_()
+            t = _events_ms(lambda: lib.decompress_window_batch_dev(items, st, False), args.reps)
+            lib.decode_status(st)
+            assert torch.equal(out, whole_src), (k, name)
+            r[name] = t
+            r[name + "_kernels"] = lib.last_kernels()
+        res.append(r)
+    return {"windows": res}
+
+
+def leg_d(args):
+    import torch
+    from zipnn_amd import ResidentCheckpoint, _capi
+    lib = _capi.lib()
+    sd, per = _blocks(max(args.layers, 2))
+    store = ResidentCheckpoint.from_state_dict(sd, "cuda:0")
+    scratch = [torch.empty(max(store.scratch_bytes(n) for n in per), dtype=torch.uint8, device="cuda") for _ in range(2)]
+    plans = [store.plan(per[i], into=scratch[i]) for i in range(2)]
+    items = [[store._entries[k].window(0, store._entries[k].chunks, plans[i].tensors[k].data_ptr()) for k in per[i]] for i in range(2)]
+    st = torch.cuda.current_stream().cuda_stream
+    out = {}
+    for name, first, second in (("plan_run", lambda: plans[0].run(), lambda: plans[1].run()),
+                                ("batch_call", lambda: lib.decompress_window_batch_dev(items[0], st, False), lambda: lib.decompress_window_batch_dev(items[1], st, False))):
+        ts = []
+        for _ in range(args.reps + 3):
+            torch.cuda.synchronize()
+            for _ in range(4):
+                first()                                   # earlier decodes, still running when the next one is enqueued
+            t0 = time.perf_counter(); second(); t1 = time.perf_counter()
+            ts.append((t1 - t0) * 1e6)
+        torch.cuda.synchronize()
+        lib.decode_status(st)
+        for i in range(2):
+            for k in per[i]:
+                assert _same(plans[i].tensors[k], sd[k]), k
+        out[name] = {"median_us": statistics.median(ts[3:]), "min_us": min(ts[3:]), "reps": args.reps}
+    for p in plans:
+        p.close()
+    return {"enqueue_while_busy": out, "tensors_per_block": len(per[0])}
+
+
+def leg_e(args):
+    import torch
+    from zipnn_amd import ResidentCheckpoint
+    torch.manual_seed(5)
+    hidden, inter = 4096, 14336
+
+    class Block(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.up, self.down = torch.nn.Linear(hidden, inter, bias=False), torch.nn.Linear(inter, hidden, bias=False)
+
+        def forward(self, x):
+            return x + self.down(torch.nn.functional.silu(self.up(x)))
+    model = torch.nn.Sequential(*[Block() for _ in range(args.layers)]).to(torch.bfloat16).to("cuda").eval()
+    for p in model.parameters():
+        p.data.mul_(0.3)
+    sd = {k: v.clone() for k, v in model.state_dict().items()}
+    res = {"layers": args.layers, "batches": []}
+    store = ResidentCheckpoint.from_state_dict(sd, "cuda:0")
+    res["original_bytes"], res["resident_bytes"] = store.nbytes, store.resident_bytes
+    for batch in (1, 16, 256):
+        x = torch.randn(batch, hidden, device="cuda", dtype=torch.bfloat16)
+        with torch.no_grad():
+            ref = model(x)
+            plain = _events_ms(lambda: model(x), args.reps)
+            handle = store.hook(model)
+            assert torch.equal(model(x), ref)
+            hooked = _events_ms(lambda: model(x), args.reps)
+            handle.status()
+            handle.remove()
+            assert torch.equal(model(x), ref)
+        res["batches"].append({"batch": batch, "plain": plain, "hooked": hooked, "scratch_bytes": int(handle.scratch.numel())})
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--layers", type=int, default=4)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--leg", default=None)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resident_decode"))
+    args = ap.parse_args()
+    if args.leg:                                          # a child: one leg, its result as one JSON line
+        print("RESULT " + json.dumps(globals()["leg_" + args.leg](args)))
+        return 0
+    results = {}
+    for leg, limit in LEG_SECONDS.items():
+        p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--layers", str(args.layers), "--reps", str(args.reps)],
+                           capture_output=True, text=True)
+        line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+        if p.returncode != 0 or not line:
+            print(f"leg {leg} failed (exit {p.returncode}); nothing further is started\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}")
+            return 1
+        results[leg] = json.loads(line[0][7:])
+        print(f"leg {leg}: ok", flush=True)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    json.dump(results, open(args.out + ".json", "w"), indent=1)
+    a, b, c, d, e = (results[k] for k in "abcde")
+    lines = [f"resident checkpoint probe: {a['layers']} Llama-3-8B blocks, bf16 N(0, 0.02), every timed result checked against its source",
+             f"(a) resident {a['resident_bytes']} of {a['original_bytes']} bytes: {a['ratio']:.4f}",
+             "(b) plan.run per block (device events, median): " + ", ".join(f"{x['median_ms']:.3f} ms ({x['gb_per_s']:.0f} GB/s)" for x in b["blocks"])]
+    for w in c["windows"]:
+        lines.append(f"(c) {w['chunks']} chunks: window {w['window']['median_ms']:.4f} / {w['window_again']['median_ms']:.4f} ms, whole tensor {w['whole']['median_ms']:.4f} / {w['whole_again']['median_ms']:.4f} ms"
+                     f"   [{w['window_kernels']} | {w['whole_kernels']}]")
+    q = d["enqueue_while_busy"]
+    lines.append(f"(d) host time to enqueue a block of {d['tensors_per_block']} tensors behind running decodes: plan.run {q['plan_run']['median_us']:.1f} us, batched call {q['batch_call']['median_us']:.1f} us (median)")
+    for x in e["batches"]:
+        lines.append(f"(e) forward of {e['layers']} MLP blocks, batch {x['batch']}: plain {x['plain']['median_ms']:.3f} ms, hooked {x['hooked']['median_ms']:.3f} ms")
+    open(args.out + ".txt", "w").write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

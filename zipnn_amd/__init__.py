@@ -5,8 +5,9 @@ zipnn_safetensors`, reference zipnn/__init__.py:1); `zipnn_hf` is outside this
 repository's scope and raises NotImplementedError.
 """
 from .zipnn import ZipNN, SafeOpen, zipnn_safetensors, zipnn_hf, decompress_safetensors_tensor  # noqa: F401
+from .resident import ResidentCheckpoint  # noqa: F401
 
-__all__ = ["ZipNN", "SafeOpen", "zipnn_safetensors", "zipnn_hf", "decompress_safetensors_tensor"]
+__all__ = ["ZipNN", "SafeOpen", "zipnn_safetensors", "zipnn_hf", "decompress_safetensors_tensor", "ResidentCheckpoint"]
 
 
 def install_as_zipnn():

@@ -38,6 +38,17 @@ ZN_BATCH_ITEM_FMT = "<QQQQiii4xQQ"          # struct zn_batch_item as struct.pac
 assert ctypes.sizeof(ZnBatchItem) == 64
 
 
+class ZnWindowItem(ctypes.Structure):
+    """struct zn_window_item of include/zipnn_hip.h"""
+    _fields_ = [("d_body", ctypes.c_void_p), ("body_len", ctypes.c_size_t), ("orig_size", ctypes.c_size_t),
+                ("chunk_lo", ctypes.c_size_t), ("chunk_hi", ctypes.c_size_t), ("d_dst", ctypes.c_void_p),
+                ("num_buf", ctypes.c_int), ("bits_mode", ctypes.c_int), ("bytes_mode", ctypes.c_int),
+                ("chunk", ctypes.c_size_t), ("d_delta", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(ZnWindowItem) == 80
+
+
 class ZnCBatchItem(ctypes.Structure):
     """struct zn_cbatch_item of include/zipnn_hip.h"""
     _fields_ = [("d_src", ctypes.c_void_p), ("n", ctypes.c_size_t), ("num_buf", ctypes.c_int), ("bits_mode", ctypes.c_int),
@@ -114,6 +125,14 @@ class ZnLib:
         L.zn_compress_batch_dev.argtypes = [ctypes.POINTER(ZnCBatchItem), sz, vp]
         L.zn_decompress_batch_dev.restype = ci
         L.zn_decompress_batch_dev.argtypes = [ctypes.POINTER(ZnBatchItem), sz, vp, ci]
+        L.zn_decompress_window_batch_dev.restype = ci
+        L.zn_decompress_window_batch_dev.argtypes = [ctypes.POINTER(ZnWindowItem), sz, vp, ci]
+        L.zn_plan_create.restype = ci
+        L.zn_plan_create.argtypes = [ctypes.POINTER(ZnWindowItem), sz, vpp]
+        L.zn_plan_run.restype = ci
+        L.zn_plan_run.argtypes = [vp, vp, ci]
+        L.zn_plan_destroy.restype = ci
+        L.zn_plan_destroy.argtypes = [vp]
         L.zn_copy_to_device.restype = ci; L.zn_copy_to_device.argtypes = [vp, vp, sz]
         L.zn_copy_to_host.restype = ci; L.zn_copy_to_host.argtypes = [vp, vp, sz]
         L.zn_release_workspace.restype = ci
@@ -366,6 +385,36 @@ class ZnLib:
         for loaders that hand over hundreds of tensors per call."""
         buf = (ctypes.c_char * len(packed)).from_buffer_copy(packed)
         self._check(self._L.zn_decompress_batch_dev(ctypes.cast(buf, ctypes.POINTER(ZnBatchItem)), count, stream, 1 if check else 0))
+
+    @staticmethod
+    def _window_items(items):
+        items = list(items)
+        arr = (ZnWindowItem * max(len(items), 1))()
+        for i, it in enumerate(items):
+            bp, bl, nb, bi, by, ch, n, lo, hi, dp = it[:10]
+            arr[i].d_delta = it[10] if len(it) > 10 else None
+            arr[i].d_body = bp; arr[i].body_len = bl; arr[i].orig_size = n; arr[i].chunk_lo = lo; arr[i].chunk_hi = hi
+            arr[i].d_dst = dp; arr[i].num_buf = nb; arr[i].bits_mode = bi; arr[i].bytes_mode = by; arr[i].chunk = ch
+        return arr, len(items)
+
+    def decompress_window_batch_dev(self, items, stream=0, check=True):
+        """zn_decompress_window_batch_dev.  items: iterable of (body_ptr, body_len, num_buf, bits_mode, bytes_mode, chunk, orig_size,
+        chunk_lo, chunk_hi, dst_ptr[, delta_ptr]): chunks [chunk_lo, chunk_hi) of the WHOLE body at body_ptr (device memory) -> dst_ptr."""
+        arr, n = self._window_items(items)
+        self._check(self._L.zn_decompress_window_batch_dev(arr, n, stream, 1 if check else 0))
+
+    def plan_create(self, items):
+        """zn_plan_create over items as for decompress_window_batch_dev -> an opaque plan handle (plan_run / plan_destroy)."""
+        arr, n = self._window_items(items)
+        h = ctypes.c_void_p(None)
+        self._check(self._L.zn_plan_create(arr, n, ctypes.byref(h)))
+        return h
+
+    def plan_run(self, plan, stream=0, check=True):
+        self._check(self._L.zn_plan_run(plan, stream, 1 if check else 0))
+
+    def plan_destroy(self, plan):
+        self._check(self._L.zn_plan_destroy(plan))
 
     def decode_status(self, stream=0):
         """zn_decode_status: wait for `stream`, raise what the last check=False decode call on this device would have raised."""

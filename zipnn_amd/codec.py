@@ -171,6 +171,36 @@ def decompress_device_batch(lib, items, check=True, into=None):
     return outs
 
 
+def window_bytes(chunk, orig_size, chunk_lo, chunk_hi):
+    """Bytes that chunks [chunk_lo, chunk_hi) of a tensor of orig_size bytes decode to."""
+    return max(min(chunk_hi * chunk, orig_size) - chunk_lo * chunk, 0)
+
+
+def decompress_device_windows(lib, items, check=True, outs=None):
+    """Chunk windows of device-resident bodies, one set of kernel launches (zn_decompress_window_batch_dev): nothing is copied or re-based,
+    the kernels read the window's rows of the WHOLE body's size tables.
+    items: iterable of (body, num_buf, bits_mode, bytes_mode, chunk, orig_size, chunk_lo, chunk_hi[, delta]) with `body` the whole frame body
+    (uint8 tensor on the device) and `delta` an optional uint8 base of the WHOLE tensor (orig_size bytes).  outs: optional list of uint8
+    destinations (window_bytes(...) bytes each).  Returns the list of decoded uint8 tensors (same device)."""
+    items = [(it[0].contiguous(),) + tuple(it[1:8]) + ((it[8].contiguous() if len(it) > 8 and it[8] is not None else None),) for it in items]
+    if not items:
+        return []
+    dev = items[0][0].device
+    for (b, _, _, _, _, n, _, _, d) in items:
+        if d is not None and (d.dtype != torch.uint8 or d.numel() != n or d.device != b.device):
+            raise ValueError("delta base must be a uint8 tensor of orig_size bytes on the same device")
+    sizes = [window_bytes(ch, n, lo, hi) for (_, _, _, _, ch, n, lo, hi, _) in items]
+    if outs is None:
+        outs = [torch.empty(sz, dtype=torch.uint8, device=dev) for sz in sizes]
+    elif len(outs) != len(items) or any(o.numel() < sz or o.dtype != torch.uint8 or not o.is_contiguous() for o, sz in zip(outs, sizes)):
+        raise ValueError("outs: one contiguous uint8 destination of the window's size per item")
+    with torch.cuda.device(dev) if dev.type == "cuda" else _nullctx():
+        lib.decompress_window_batch_dev(((b.data_ptr(), b.numel(), nb, bi, by, ch, n, lo, hi, o.data_ptr() if sz else 0,
+                                          d.data_ptr() if (d is not None and n) else None)
+                                         for (b, nb, bi, by, ch, n, lo, hi, d), o, sz in zip(items, outs, sizes)), _stream_handle(items[0][0]), check)
+    return outs
+
+
 def compress_device_batch(lib, items, gap=0, return_arena=False):
     """Many tensors, one launch per stage (zn_compress_batch_dev), one read-back of all lengths.
     items: iterable of (flat_uint8_device_tensor, num_buf, bits_mode, bytes_mode, chunk, threshold[, delta]).

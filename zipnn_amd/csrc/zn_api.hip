@@ -6,6 +6,7 @@
 #include "zn_internal.hpp"
 #include "zn_host_pipe.hpp"
 
+#include <memory>
 #include <mutex>
 #include <atomic>
 #include <condition_variable>
@@ -395,54 +396,87 @@ static int zn_decode_overlap_on() {
   if (x < 0) { const char* e = getenv("ZIPNN_AMD_DECODE_OVERLAP"); x = (e && e[0] >= '0' && e[0] <= '9') ? e[0] - '0' : 1; v.store(x, std::memory_order_relaxed); }
   return x;
 }
-static int decompress_items(const zn_batch_item* items, size_t count, hipStream_t stream, int check) {
-  if (count && !items) return ZN_E_ARG;
+// What a decode call launches: the segments of its tensors / chunk windows by plane count, and the form choice.  Built once (build_segments: every argument and
+// geometry check, the knobs read), launched by launch_segments — once by the one-shot entry points, any number of times by a plan (zn_plan_run).
+struct DecodeSet {
   std::vector<ZnSeg> segs[3];                    // by plane count: 1, 2, 4
-  uint64_t pk_of[3] = {0, 0, 0}, k_of[3] = {0, 0, 0}; uint64_t wg_of[3] = {0, 0, 0}, tail_of[3] = {0, 0, 0};
+  uint64_t pk_of[3] = {0, 0, 0}, k_of[3] = {0, 0, 0}, wg_of[3] = {0, 0, 0}, tail_of[3] = {0, 0, 0};
   bool delta_of[3] = {false, false, false}, rest_ok[3] = {true, true, true};
+  uint64_t total_chunks = 0;
+  int wide = 0;
+};
+// bytes and chunks of an item's window (arguments not yet checked: clamped, so that nothing here can wrap)
+static inline void zn_window_of(const zn_window_item& it, uint64_t* n, uint64_t* k) {
+  *n = 0; *k = 0;
+  if (!it.chunk) return;
+  const uint64_t kb = zn_num_chunks(it.orig_size, it.chunk);
+  const uint64_t hi = it.chunk_hi < kb ? it.chunk_hi : kb, lo = it.chunk_lo < hi ? it.chunk_lo : hi;
+  const uint64_t end = hi == kb ? (uint64_t)it.orig_size : hi * it.chunk;
+  *n = end - lo * it.chunk; *k = hi - lo;
+}
+static int build_segments(const zn_window_item* items, size_t count, DecodeSet& D) {
+  if (count && !items) return ZN_E_ARG;
+  std::vector<ZnSeg>* segs = D.segs;
+  uint64_t* pk_of = D.pk_of; uint64_t* k_of = D.k_of; uint64_t* wg_of = D.wg_of; uint64_t* tail_of = D.tail_of;
+  bool* delta_of = D.delta_of; bool* rest_ok = D.rest_ok;
   uint64_t total_chunks = 0;
   bool any_delta = false;
   uint64_t full_chunks = 0; bool all_rotated = true; uint64_t tail_wgs = 0;
   uint64_t kq[3] = {0, 0, 0};                    // chunks per launch (one launch per plane count)
   for (size_t i = 0; i < count; i++) {
-    total_chunks += zn_num_chunks(items[i].orig_size, items[i].chunk); if (items[i].d_delta) any_delta = true;
+    uint64_t wn, wk; zn_window_of(items[i], &wn, &wk);      // (a window is a tensor of its own to everything that follows)
+    total_chunks += wk; if (items[i].d_delta) any_delta = true;
     // (FULL chunks: a partial last chunk is the tail workgroups' — the workgroup its group index maps to only skips it, and counting it would push a tensor of exactly
     //  n rounds into n + 1: 6 144 chunks + a tail took single-chunk groups, 0.64 ms, where three-chunk groups take 0.59)
-    if (items[i].chunk) kq[items[i].num_buf == 1 ? 0 : items[i].num_buf == 2 ? 1 : 2] += items[i].orig_size / items[i].chunk;
-    if (items[i].chunk) full_chunks += items[i].orig_size / items[i].chunk;
+    if (items[i].chunk) kq[items[i].num_buf == 1 ? 0 : items[i].num_buf == 2 ? 1 : 2] += wn / items[i].chunk;
+    if (items[i].chunk) full_chunks += wn / items[i].chunk;
     // (tensors without the sign rotate — fp16, fp8, integers: their Huffman planes are dense codes, which the wide kernel parses and declines)
     if (!(items[i].bits_mode == 1 && items[i].num_buf > 1)) all_rotated = false;
     // (… a partial last chunk: its tail workgroups ride at the front of the wide launch and its merge workgroups at the end of it, as in a fused launch; the tail
     //  workgroups take workgroup slots of their own — 64 MiB + 250 KB = 256 chunks + 8 took two rounds of the 16-wave form on 256 CUs, 113 µs against the 8-wave form's 73)
-    if (items[i].chunk && items[i].orig_size % items[i].chunk) tail_wgs += 4u * (uint64_t)(items[i].num_buf > 0 ? items[i].num_buf : 1) + 32u;      // (… + the tensor's merge workgroups at the end of the grid)
+    if (items[i].chunk && wn % items[i].chunk) tail_wgs += 4u * (uint64_t)(items[i].num_buf > 0 ? items[i].num_buf : 1) + 32u;      // (… + the tensor's merge workgroups at the end of the grid)
   }
   const int wide = zn_decode_use_wide(full_chunks, any_delta, all_rotated, tail_wgs);       // small calls: a 16-wave workgroup per full chunk (zn_decode_wide.hpp)
   uint32_t ncg_of[3];
   for (int q = 0; q < 3; q++) ncg_of[q] = wide ? 1u : zn_decode_fused_group(kq[q]);
   for (size_t i = 0; i < count; i++) {
-    const zn_batch_item& it = items[i];
+    const zn_window_item& it = items[i];
     ZnSeg sg;
-    int rc = check_geom(it.orig_size, it.num_buf, it.bytes_mode, it.chunk, &sg.g, it.bits_mode);
+    int rc = check_geom(it.orig_size, it.num_buf, it.bytes_mode, it.chunk, &sg.g, it.bits_mode);      // the BODY's geometry …
     if (rc) return rc;
+    if (it.chunk_lo > it.chunk_hi || it.chunk_hi > sg.g.K) return ZN_E_ARG;
+    sg.kb = (uint32_t)sg.g.K; sg.c_lo = (uint32_t)it.chunk_lo;                                        // (check_geom: P·K < 2^31)
     if (it.body_len < 9u * (size_t)sg.g.P * sg.g.K) return ZN_E_CORRUPT;
-    if (it.orig_size == 0) continue;
+    if (it.chunk_lo == it.chunk_hi) continue;
     if (!it.d_body || !it.d_dst) return ZN_E_ARG;
+    { uint64_t wn, wk; zn_window_of(it, &wn, &wk); sg.g.n = wn; sg.g.K = wk; }                        // … and the window's, which is what the kernels decode
     const int q = sg.g.P == 1 ? 0 : sg.g.P == 2 ? 1 : 2;
     const uint32_t ncg = ncg_of[q];
     sg.body = (const uint8_t*)it.d_body; sg.body_len = it.body_len; sg.dst = (uint8_t*)it.d_dst;
-    sg.xr = (const uint8_t*)it.d_delta;
+    sg.xr = it.d_delta ? (const uint8_t*)it.d_delta + (uint64_t)it.chunk_lo * it.chunk : nullptr;
     if (sg.xr) delta_of[q] = true;
     // (a LARGE call in a geometry the fused kernel takes no chunk of — its rule: whole rows per stream, a 16-byte aligned destination — goes to the generic
     //  KERNELS, which spread it over the whole chip with one wave per plane; the fused kernel's rest instance decodes the odd chunk, or the odd small tensor)
     { const uint64_t unit = 64ull * (sg.g.P == 1 ? 16u : 8u);
       if ((it.chunk % (4ull * sg.g.P * unit) != 0 || (((uintptr_t)it.d_dst) & 15u) != 0) && total_chunks > 1024u) rest_ok[q] = false; }
-    sg.chunk0 = k_of[q]; sg.desc0 = pk_of[q]; sg.wg0 = (uint32_t)wg_of[q]; sg.ncg = ncg;
-    sg.tail0 = (uint32_t)tail_of[q]; sg.has_tail = (it.orig_size % it.chunk) != 0 ? 1u : 0u;   // partial last chunk
+    sg.chunk0 = (uint32_t)k_of[q]; sg.desc0 = (uint32_t)pk_of[q]; sg.wg0 = (uint32_t)wg_of[q]; sg.ncg = ncg;
+    sg.tail0 = (uint32_t)tail_of[q]; sg.has_tail = (sg.g.n % it.chunk) != 0 ? 1u : 0u;   // partial last chunk
     if (sg.has_tail) tail_of[q] += sg.g.P;
     k_of[q] += sg.g.K; pk_of[q] += (uint64_t)sg.g.P * sg.g.K; wg_of[q] += (sg.g.K + ncg - 1u) / ncg;
     if (pk_of[q] > 0x7FFFFFFFull || wg_of[q] > 0x7FFFFFFFull) return ZN_E_ARG;
     segs[q].push_back(sg);
   }
+  D.total_chunks = total_chunks; D.wide = wide;
+  return ZN_OK;
+}
+
+// d_table: the segment table already in device memory (a plan's: 1-plane segments, then 2-, then 4-plane ones), or null — the call's own, staged through the
+// workspace's pinned buffer, which is the one thing here that makes the host wait for earlier device work.
+static int launch_segments(const DecodeSet& D, const ZnSeg* d_table, hipStream_t stream, int check) {
+  const std::vector<ZnSeg>* segs = D.segs;
+  const uint64_t* pk_of = D.pk_of; const uint64_t* k_of = D.k_of; const uint64_t* wg_of = D.wg_of; const uint64_t* tail_of = D.tail_of;
+  const bool* delta_of = D.delta_of; bool rest_ok[3] = {D.rest_ok[0], D.rest_ok[1], D.rest_ok[2]};
+  const uint64_t total_chunks = D.total_chunks; const int wide = D.wide;
   const uint64_t all_k = k_of[0] + k_of[1] + k_of[2], all_pk = pk_of[0] + pk_of[1] + pk_of[2];
   if (all_k == 0) return ZN_OK;
   int dev = 0;
@@ -454,6 +488,7 @@ static int decompress_items(const zn_batch_item* items, size_t count, hipStream_
   int rc;
   const size_t nseg_all = segs[0].size() + segs[1].size() + segs[2].size();
   const bool table = nseg_all > 1;
+  const bool staged = table && !d_table;        // (the table goes through the pinned staging buffer)
   if ((rc = ws_reserve(w, WS_META_C, all_pk * sizeof(ZnPlaneDesc)))) return rc;
   if ((rc = ws_reserve(w, WS_META_B, all_k))) return rc;                     // per-chunk "done by the fused kernel" flags
   if ((rc = ws_reserve(w, WS_ENC, all_pk))) return rc;                       // … and the same per (plane, chunk)
@@ -463,7 +498,7 @@ static int decompress_items(const zn_batch_item* items, size_t count, hipStream_
   if ((rc = ws_reserve(w, WS_META_A, sync_off + 2u * sizeof(uint32_t) * all_tail))) return rc;
   if ((rc = ws_reserve(w, WS_WORDS, ZN_WORDS_BYTES))) return rc;
   if ((rc = ws_host_words(w))) return rc;
-  if (table) {
+  if (staged) {
     if ((rc = ws_reserve(w, WS_SEGS, nseg_all * sizeof(ZnSeg)))) return rc;
     if (w.h_segs_cap < nseg_all) {
       if (w.h_segs) { ZN_HIP(hipHostFree(w.h_segs)); w.h_segs = nullptr; w.h_segs_cap = 0; }
@@ -482,7 +517,7 @@ static int decompress_items(const zn_batch_item* items, size_t count, hipStream_
   bool status_zeroed = false;
   if (!wide || all_tail) { ZN_HIP(hipMemsetAsync(d_status, 0, 4 * sizeof(uint32_t), stream)); status_zeroed = true; }
   if (all_tail) ZN_HIP(hipMemsetAsync(w.buf[WS_META_A], 0, sync_off + 2u * sizeof(uint32_t) * all_tail, stream));
-  if (table) {
+  if (staged) {
     // the previous batched call may still be reading the pinned staging: wait for it on the host
     ZN_HIP(hipEventSynchronize(w.busy));
     size_t o = 0;
@@ -517,7 +552,7 @@ static int decompress_items(const zn_batch_item* items, size_t count, hipStream_
     const int P = q == 0 ? 1 : q == 1 ? 2 : 4;
     stream = !overlap ? stream_main : (q == 0 ? w.dstream : w.dstream2);
     seg_base = seg_b[q]; k_base = k_b[q]; pk_base = pk_b[q]; tail_base = tail_b[q];
-    const ZnSeg* d_segs = table ? (const ZnSeg*)w.buf[WS_SEGS] + seg_base : nullptr;
+    const ZnSeg* d_segs = table ? (d_table ? d_table : (const ZnSeg*)w.buf[WS_SEGS]) + seg_base : nullptr;
     const uint32_t nseg = (uint32_t)segs[q].size();
     uint8_t* d_done = (uint8_t*)w.buf[WS_META_B] + k_base;
     ZnPlaneDesc* d_descs = (ZnPlaneDesc*)w.buf[WS_META_C] + pk_base;
@@ -547,14 +582,14 @@ static int decompress_items(const zn_batch_item* items, size_t count, hipStream_
     if (ej != hipSuccess || ej2 != hipSuccess) {           // the join itself failed: drain the side streams on the host, so that nothing of this call is still running when it returns
       (void)hipStreamSynchronize(w.dstream); (void)hipStreamSynchronize(w.dstream2);
       t_hip_err = std::string("two-stream join: ") + hipGetErrorString(ej != hipSuccess ? ej : ej2); (void)hipGetLastError();
-      (void)ws_release(w, stream_main, table);
+      (void)ws_release(w, stream_main, staged);
       return ZN_E_HIP;
     }
   }
   { const hipError_t el = hipGetLastError();               // a launch that failed: the workspace is still handed back in stream order (the side streams are joined above)
-    if (el != hipSuccess) { t_hip_err = std::string("kernel launch: ") + hipGetErrorString(el); (void)ws_release(w, stream_main, table); return ZN_E_HIP; } }
+    if (el != hipSuccess) { t_hip_err = std::string("kernel launch: ") + hipGetErrorString(el); (void)ws_release(w, stream_main, staged); return ZN_E_HIP; } }
   if (check) ZN_HIP(hipMemcpyAsync(w.h_status, d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  if ((rc = ws_release(w, stream, table))) return rc;
+  if ((rc = ws_release(w, stream, staged))) return rc;
   if (check) {
     ZN_HIP(hipStreamSynchronize(stream));
     const uint32_t st = *w.h_status;
@@ -565,13 +600,26 @@ static int decompress_items(const zn_batch_item* items, size_t count, hipStream_
   return ZN_OK;
 }
 
+static inline zn_window_item zn_whole_window(const zn_batch_item& it) {      // the window [0, K): the whole tensor
+  zn_window_item w;
+  w.d_body = it.d_body; w.body_len = it.body_len; w.orig_size = it.orig_size; w.chunk_lo = 0; w.chunk_hi = zn_num_chunks(it.orig_size, it.chunk);
+  w.d_dst = it.d_dst; w.num_buf = it.num_buf; w.bits_mode = it.bits_mode; w.bytes_mode = it.bytes_mode; w.chunk = it.chunk; w.d_delta = it.d_delta;
+  return w;
+}
+static int decompress_windows(const zn_window_item* items, size_t count, hipStream_t stream, int check) {
+  DecodeSet D;
+  const int rc = build_segments(items, count, D);
+  return rc ? rc : launch_segments(D, nullptr, stream, check);
+}
+
 int zn_decompress_delta_dev(const void* d_body, size_t body_len, const void* d_delta, int num_buf, int bits_mode, int bytes_mode,
                             size_t chunk, size_t orig_size, void* d_dst, void* stream_, int check) {
   zn_batch_item it; it.d_delta = d_delta;
   it.d_body = d_body; it.body_len = body_len; it.d_dst = d_dst; it.orig_size = orig_size;
   it.num_buf = num_buf; it.bits_mode = bits_mode; it.bytes_mode = bytes_mode; it.chunk = chunk;
   try {
-    return decompress_items(&it, 1, (hipStream_t)stream_, check);
+    const zn_window_item w = zn_whole_window(it);
+    return decompress_windows(&w, 1, (hipStream_t)stream_, check);
   } catch (...) { return ZN_E_ALLOC; }
 }
 
@@ -582,8 +630,82 @@ int zn_decompress_dev(const void* d_body, size_t body_len, int num_buf, int bits
 
 int zn_decompress_batch_dev(const zn_batch_item* items, size_t count, void* stream_, int check) {
   try {                                          // (the segment lists are std::vectors: nothing may unwind through the C ABI)
-    return decompress_items(items, count, (hipStream_t)stream_, check);
+    if (count && !items) return ZN_E_ARG;
+    std::vector<zn_window_item> win(count);
+    for (size_t i = 0; i < count; i++) win[i] = zn_whole_window(items[i]);
+    return decompress_windows(win.data(), count, (hipStream_t)stream_, check);
   } catch (...) { return ZN_E_ALLOC; }
+}
+
+int zn_decompress_window_batch_dev(const zn_window_item* items, size_t count, void* stream_, int check) {
+  try {
+    return decompress_windows(items, count, (hipStream_t)stream_, check);
+  } catch (...) { return ZN_E_ALLOC; }
+}
+
+}  // extern "C"
+// A prepared batched decode: everything build_segments works out, and the segment table in device memory of its own — zn_release_workspace frees none of it,
+// and a run stages nothing: no host-to-device copy, no wait for the pinned staging buffer that one-shot batched calls share.
+struct zn_plan {
+  DecodeSet D;
+  ZnSeg* d_table = nullptr;      // 1-plane segments, then 2-, then 4-plane ones (null: at most one segment, which travels as a kernel argument)
+  hipEvent_t last = nullptr;     // recorded behind every run: what zn_plan_destroy waits for (no stream handle is kept — see ws_acquire)
+  bool ran = false;
+  int dev = 0;
+  ~zn_plan() {                   // (on the plan's device; nothing of it is in use any more)
+    if (d_table) (void)hipFree(d_table);
+    if (last) (void)hipEventDestroy(last);
+  }
+};
+extern "C" {
+
+int zn_plan_create(const zn_window_item* items, size_t count, zn_plan** plan) {
+  if (!plan) return ZN_E_ARG;
+  *plan = nullptr;
+  try {
+    int dev = 0;
+    ZN_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64) return ZN_E_ARG;
+    std::unique_ptr<zn_plan> pl(new zn_plan());          // (whatever throws or fails below takes the plan, its table and its event with it)
+    pl->dev = dev;
+    const int rc = build_segments(items, count, pl->D);
+    if (rc) return rc;
+    std::vector<ZnSeg> all;
+    for (int q = 0; q < 3; q++) all.insert(all.end(), pl->D.segs[q].begin(), pl->D.segs[q].end());
+    if (all.size() > 1) {
+      hipError_t e = hipMalloc((void**)&pl->d_table, all.size() * sizeof(ZnSeg));
+      if (e != hipSuccess) { pl->d_table = nullptr; t_hip_err = std::string("hipMalloc: ") + hipGetErrorString(e); (void)hipGetLastError(); return ZN_E_ALLOC; }
+      ZN_HIP(hipMemcpy(pl->d_table, all.data(), all.size() * sizeof(ZnSeg), hipMemcpyHostToDevice));
+    }
+    ZN_HIP(hipEventCreateWithFlags(&pl->last, hipEventDisableTiming));
+    *plan = pl.release();
+    return ZN_OK;
+  } catch (...) { return ZN_E_ALLOC; }
+}
+
+int zn_plan_run(zn_plan* plan, void* stream_, int check) {
+  if (!plan) return ZN_E_ARG;
+  try {
+    int dev = 0;
+    ZN_HIP(hipGetDevice(&dev));
+    if (dev != plan->dev) return ZN_E_ARG;       // (the table and everything it points to live on the device the plan was made on)
+    const int rc = launch_segments(plan->D, plan->d_table, (hipStream_t)stream_, check);
+    // (also behind a run that failed part-way: some of its kernels may be queued and read the table)
+    if (plan->d_table) { if (hipEventRecord(plan->last, (hipStream_t)stream_) == hipSuccess) plan->ran = true; else { (void)hipGetLastError(); (void)hipDeviceSynchronize(); } }
+    return rc;
+  } catch (...) { return ZN_E_ALLOC; }
+}
+
+int zn_plan_destroy(zn_plan* plan) {
+  if (!plan) return ZN_OK;
+  int rc = ZN_OK;
+  {
+    DeviceScope scope(plan->dev);
+    // the plan's last run — that stream's work up to it, no other stream's — is over before the table goes
+    if (!scope.ok || (plan->ran && hipEventSynchronize(plan->last) != hipSuccess)) { t_hip_err = "zn_plan_destroy"; (void)hipGetLastError(); (void)hipDeviceSynchronize(); rc = ZN_E_HIP; }
+    delete plan;
+  }
+  return rc;
 }
 
 // Large host buffers take a three-stage pipeline over slices of the chunks — upload slice i + 1 | code slice i | download slice i - 1 —

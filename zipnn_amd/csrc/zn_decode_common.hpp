@@ -11,7 +11,7 @@
 // chunk) index, 2 = chunk index.  Wave-uniform (scalar loads); the last segment with key ≤ b.
 // ---------------------------------------------------------------------------
 template <int KEY>
-__device__ __forceinline__ uint64_t zn_seg_key(const ZnSeg& s) { return KEY == 0 ? (uint64_t)s.wg0 : KEY == 1 ? s.desc0 : KEY == 2 ? s.chunk0 : (uint64_t)s.tail0; }
+__device__ __forceinline__ uint64_t zn_seg_key(const ZnSeg& s) { return KEY == 0 ? (uint64_t)s.wg0 : KEY == 1 ? (uint64_t)s.desc0 : KEY == 2 ? (uint64_t)s.chunk0 : (uint64_t)s.tail0; }
 template <int KEY>
 __device__ __forceinline__ ZnSeg zn_find_seg(const ZnSeg& one, const ZnSeg* __restrict__ segs, uint32_t nseg, uint64_t b) {
   // (a struct VALUE that is overwritten, not a choice between two struct ADDRESSES: returning `one` or `segs[lo]` made the compiler keep the
@@ -34,23 +34,29 @@ struct ZnPcMeta { uint64_t off; uint32_t csize; uint32_t plen; uint32_t type; ui
 // Everything here comes out of an untrusted frame: every sum is checked against what is left of the body BEFORE it
 // is formed, so that no crafted cumSizes entry can wrap the 64-bit arithmetic and move `off` outside [0, body_len)
 // (a plane total of 2^64 - 9PK - 4096 used to give the next plane a base 4096 bytes before the body).
-__device__ inline ZnPcMeta zn_pc_meta(const ZnGeom& g, const uint8_t* body, uint64_t body_len, uint32_t p, uint64_t c) {
+// `g` is the geometry of the chunk WINDOW the segment decodes and `c` a chunk of it; the tables belong to the whole body: kb chunks (their stride, and where the
+// plane totals stand), the window's first chunk is the body's c_lo (ZnSeg::kb / c_lo; a whole tensor: kb == g.K, c_lo == 0).  kb is as untrusted as the body: a
+// wrong one fails the first check or reads other entries of the same body, never outside it.
+__device__ inline ZnPcMeta zn_pc_meta(const ZnGeom& g, uint32_t kb, uint32_t c_lo, const uint8_t* body, uint64_t body_len, uint32_t p, uint64_t c) {
   ZnPcMeta m;
-  const uint64_t PK = (uint64_t)g.P * g.K;
-  const uint8_t* cum = body + PK;                       // u64 [P][K], inclusive, unaligned
-  bool ok = (PK <= body_len / 9u);                      // types + cumSizes fit
+  const uint64_t cb64 = (uint64_t)c_lo + c;             // the body's index of chunk c
+  const uint64_t PK = (uint64_t)g.P * kb;               // (32 bits each: the product cannot wrap)
+  bool ok = (PK <= 0x7FFFFFFFull) && (PK <= body_len / 9u) && (cb64 < kb);      // types + cumSizes fit, and the entry is one of theirs
+  const uint32_t cb = (uint32_t)cb64;
+  const uint8_t* cum = body + PK;                       // u64 [P][kb], inclusive, unaligned (only read when ok; every entry index below is < PK < 2^31)
   uint64_t base = 9u * PK;                              // payload start
   for (uint32_t q = 0; q < p && ok; q++) {
-    const uint64_t t = zn_ld64(cum + 8u * ((uint64_t)q * g.K + g.K - 1));   // total of plane q
+    const uint64_t t = zn_ld64(cum + 8ull * (q * kb + kb - 1u));   // total of plane q
     if (t > body_len - base) ok = false; else base += t;
   }
+  const uint32_t e = p * kb + cb;                       // the entry
   uint64_t hi = 0, lo = 0;
   if (ok) {
-    hi = zn_ld64(cum + 8u * ((uint64_t)p * g.K + c));
-    lo = c ? zn_ld64(cum + 8u * ((uint64_t)p * g.K + c - 1)) : 0;
+    hi = zn_ld64(cum + 8ull * e);
+    lo = cb ? zn_ld64(cum + 8ull * (e - 1u)) : 0;
     ok = (hi >= lo) && (hi - lo <= 0xFFFFFFFFull) && (hi <= body_len - base);
   }
-  m.type = ok ? body[(uint64_t)p * g.K + c] : 0xFFu;
+  m.type = ok ? body[e] : 0xFFu;
   m.plen = zn_plane_len(zn_chunk_len(g, c), g.P, p);
   m.ok = ok ? 1u : 0u;
   m.csize = ok ? (uint32_t)(hi - lo) : 0u;

@@ -729,7 +729,7 @@ __device__ void zn_decode_tail_wg(ZnFusedLds& L_, const ZnSeg& one, const ZnSeg*
   const uint32_t p = b - S.tail0;
   const uint64_t c = g.K - 1u;
   ZN_PT_DECL;
-  const ZnPcMeta m = zn_pc_meta(g, body, body_len, p, c);
+  const ZnPcMeta m = zn_pc_meta(g, S.kb, S.c_lo, body, body_len, p, c);
   if (!(m.ok && m.type == 1u && m.csize > 1u && m.csize < m.plen && m.plen >= ZN_TAIL_WG_MIN_PLANE && m.plen <= 4u * ZN_TAIL_SEGPAD)) return;
   const uint8_t* src = body + m.off;
   if (wave == 0) {
@@ -906,7 +906,7 @@ __global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void zn_k_decode
   ZnSeg S;
   S.g.n = zn_uniform64(S_.g.n); S.g.chunk = zn_uniform64(S_.g.chunk); S.g.K = zn_uniform64(S_.g.K); S.g.P = zn_uniform(S_.g.P); S.g.rot = zn_uniform(S_.g.rot);
   S.body = (const uint8_t*)zn_uniform64((uint64_t)S_.body); S.body_len = zn_uniform64(S_.body_len); S.dst = (uint8_t*)zn_uniform64((uint64_t)S_.dst);
-  S.chunk0 = zn_uniform64(S_.chunk0); S.desc0 = zn_uniform64(S_.desc0); S.wg0 = zn_uniform(S_.wg0); S.ncg = zn_uniform(S_.ncg);
+  S.chunk0 = zn_uniform(S_.chunk0); S.desc0 = zn_uniform(S_.desc0); S.wg0 = zn_uniform(S_.wg0); S.ncg = zn_uniform(S_.ncg);
   S.tail0 = zn_uniform(S_.tail0); S.has_tail = zn_uniform(S_.has_tail); S.xr = (const uint8_t*)zn_uniform64((uint64_t)S_.xr);
   const ZnGeom g = S.g;
   const uint8_t* __restrict__ body = ZN_GLOBAL_PTR(const uint8_t, S.body); const uint64_t body_len = S.body_len;
@@ -940,7 +940,7 @@ __global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void zn_k_decode
   // ---- metadata: one thread per (chunk, plane) ----
   if (tid < nc * (uint32_t)P) {
     const uint32_t j = tid / (uint32_t)P, p = tid % (uint32_t)P;
-    const ZnPcMeta m = zn_pc_meta(g, body, body_len, p, c0 + j);
+    const ZnPcMeta m = zn_pc_meta(g, zn_uniform(S_.kb), zn_uniform(S_.c_lo), body, body_len, p, c0 + j);
     ZnFusedPlane pl; pl.off = m.off; pl.csize = m.csize; pl.kind = 99u;   // 99 = not for this kernel
     if (m.ok && m.type <= 1u && zn_chunk_len(g, c0 + j) == g.chunk) {
       if (m.type == 0u) { if (m.csize >= plen) pl.kind = ZN_KIND_RAW; }

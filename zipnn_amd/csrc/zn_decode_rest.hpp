@@ -69,7 +69,7 @@ __device__ inline void zn_decode_plane_item(ZnPlanesLds& L, const ZnSeg& one, co
   const uint64_t pc = b - S.desc0;
   const uint32_t p = (uint32_t)(pc / g.K);
   const uint64_t c = pc % g.K;
-  const ZnPcMeta m = zn_pc_meta(g, body, body_len, p, c);
+  const ZnPcMeta m = zn_pc_meta(g, S.kb, S.c_lo, body, body_len, p, c);
   ZnPlaneDesc d; d.off = 0; d.kind = ZN_KIND_RAW; d.len = m.plen;
 
   uint32_t bad = 0;

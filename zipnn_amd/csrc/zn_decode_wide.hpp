@@ -379,8 +379,8 @@ __global__ __launch_bounds__(256 * WPS, 4) void zn_k_decode_wide(ZnSeg one, cons
   g.n = zn_uniform64(S_.g.n); g.chunk = zn_uniform64(S_.g.chunk); g.K = zn_uniform64(S_.g.K); g.P = zn_uniform(S_.g.P); g.rot = zn_uniform(S_.g.rot);
   const uint8_t* __restrict__ body = ZN_GLOBAL_PTR(const uint8_t, zn_uniform64((uint64_t)S_.body)); const uint64_t body_len = zn_uniform64(S_.body_len);
   uint8_t* __restrict__ dst = ZN_GLOBAL_PTR(uint8_t, zn_uniform64((uint64_t)S_.dst));
-  uint8_t* __restrict__ done = done_all + zn_uniform64(S_.chunk0);
-  uint8_t* __restrict__ pdone = pdone_all + zn_uniform64(S_.desc0);
+  uint8_t* __restrict__ done = done_all + zn_uniform(S_.chunk0);
+  uint8_t* __restrict__ pdone = pdone_all + zn_uniform(S_.desc0);
   const uint64_t c = (uint64_t)(wg - zn_uniform(S_.wg0));               // (ncg == 1)
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = zn_uniform(tid >> 6);
   const uint32_t plen = (uint32_t)(g.chunk / P), seg = plen / 4u;
@@ -393,7 +393,7 @@ __global__ __launch_bounds__(256 * WPS, 4) void zn_k_decode_wide(ZnSeg one, cons
 
   if (tid < (uint32_t)P) {
     const uint32_t p = tid;
-    const ZnPcMeta m = zn_pc_meta(g, body, body_len, p, c);
+    const ZnPcMeta m = zn_pc_meta(g, zn_uniform(S_.kb), zn_uniform(S_.c_lo), body, body_len, p, c);
     ZnFusedPlane pl; pl.off = m.off; pl.csize = m.csize; pl.kind = 99u;
     if (m.ok && m.type <= 1u && zn_chunk_len(g, c) == g.chunk) {
       if (m.type == 0u) { if (m.csize >= plen) pl.kind = ZN_KIND_RAW; }

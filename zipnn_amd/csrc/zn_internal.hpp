@@ -20,14 +20,23 @@ static inline size_t zn_plane_slot(size_t chunk, int P) { return ((chunk + (size
 struct ZnSeg {
   ZnGeom g;
   const uint8_t* body; uint64_t body_len; uint8_t* dst;
-  uint64_t chunk0;   // index of the tensor's first chunk in the launch-wide done[] flags  (merge kernel grid)
-  uint64_t desc0;    // index of its first (plane, chunk) in descs[]                          (planes kernel grid)
+  // (chunk0 / desc0 and the window's two words are 32 bits each — a launch, like a body, has fewer than 2^31 (plane, chunk) entries —, so that the struct
+  //  stays at the 96 bytes it had before it could describe a window: every cold path that hands a copy of it to a real function keeps that copy in private
+  //  memory.  kb and c_lo sit in what were the high halves of chunk0 and desc0: with them behind xr the rest instances spilled 4 and 16 more vector registers.)
+  uint32_t chunk0;   // index of the tensor's first chunk in the launch-wide done[] flags  (merge kernel grid)
+  uint32_t kb;       // WINDOW: chunks of the whole body — the stride of its types / cumSizes tables
+  uint32_t desc0;    // index of its first (plane, chunk) in descs[]                          (planes kernel grid)
+  uint32_t c_lo;     // WINDOW: the body's chunk index of the segment's first chunk
   uint32_t wg0;      // its first workgroup of the fused kernel
   uint32_t ncg;      // chunks per fused workgroup
   uint32_t tail0;    // a partial last chunk gets P workgroups of the tail kernel / P tail-scratch slots from here …
   uint32_t has_tail; // … if this is non-zero
   const uint8_t* xr; // delta base (orig_size bytes) the decoded bytes are XORed with on the way out, or null
+  // A segment decodes a chunk WINDOW [c_lo, c_lo + g.K) of a body of kb chunks: g describes the window (g.n bytes, g.K chunks; a window that ends at the tensor's
+  // partial last chunk is a tensor with a tail), dst / xr point at its first byte, and only the parse (zn_pc_meta) knows about the body around it.  A whole
+  // tensor: kb == g.K, c_lo == 0.
 };
+static_assert(sizeof(ZnSeg) == 96, "ZnSeg is a by-value kernel argument and a table entry: its size is part of the kernels' register and scratch budget");
 
 // ---- generic decode path (any dtype, any tail) : zn_decode_generic.hip ----
 // descs: Σ P·K entries; status: one device word; d_done: Σ K flags written by the fused kernel.

@@ -214,6 +214,33 @@ def decode_file_on_device(filename, device, compressed_only=False, timings=None,
     resident once the decode has run; the decoded tensors share the arena (they live and die together in a model load; set
     ZIPNN_AMD_LOAD_ARENA=0, or pass use_arena=False, for one allocation per tensor — what the plugin's read-ahead does, whose
     consumers may keep any subset of a shard)."""
+    from . import _capi, codec
+    up = _upload_file(filename, device)
+    if up is None:
+        return None
+    if use_arena is None:                              # (load_file: everything is returned together; SafeOpen's read-ahead passes False)
+        use_arena = os.environ.get("ZIPNN_AMD_LOAD_ARENA", "1") != "0"
+    return _decode_uploaded(_capi.lib(), codec, up.device, up.layout, up.infos, up.frames, up.arena_bytes, up.blob, use_arena, compressed_only, timings, up.marks)
+
+
+class _Uploaded:
+    """A .znn.safetensors file whose data section is on the device (_upload_file)."""
+    __slots__ = ("device", "layout", "infos", "frames", "arena_bytes", "blob", "marks")
+
+    def __init__(self, device, layout, infos, frames, arena_bytes, blob, marks):
+        self.device = device              # torch.device
+        self.layout = layout              # {name: (dtype, shape, lo, hi)}: every tensor of the container, offsets into blob
+        self.infos = infos                # the file's znn_compressed_vectors metadata
+        self.frames = frames              # per compressed tensor: (name, offset of the frame BODY in blob, end of the frame, fast_frame_params, offset in a decode arena)
+        self.arena_bytes = arena_bytes    # size of an arena that takes every decoded tensor at a 256-byte boundary
+        self.blob = blob                  # the data section: a uint8 tensor on the device
+        self.marks = marks                # perf_counter at start / headers parsed / upload done
+
+
+def _upload_file(filename, device):
+    """First half of decode_file_on_device, and how resident.ResidentCheckpoint.from_file gets its frames into HBM: every frame header parsed
+    from the host mapping, then the file's data section to the device in ONE transfer.  -> _Uploaded, or None when the container names a dtype
+    this parser does not know."""
     import contextlib
     import mmap
     import threading
@@ -235,8 +262,6 @@ def decode_file_on_device(filename, device, compressed_only=False, timings=None,
         mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if size else None
     view = memoryview(mm) if mm is not None else None
     head_len = 32 + 1 + 9 * 255                        # header + the largest shape extension (zipnn._frame_head)
-    if use_arena is None:                              # (load_file: everything is returned together; SafeOpen's read-ahead passes False)
-        use_arena = os.environ.get("ZIPNN_AMD_LOAD_ARENA", "1") != "0"
     try:
         # ---- host side: one pass over the mapping ----
         plan, total = [], 0                            # (name, lo + body_off, hi, fp, arena offset)
@@ -264,7 +289,7 @@ def decode_file_on_device(filename, device, compressed_only=False, timings=None,
             closer = threading.Thread(target=_close_mapping, daemon=True)
             closer.start()
             _PENDING_CLOSERS.append(closer)                # (joined by the next call — by then long finished — not by this one: nothing below needs the mapping gone)
-    return _decode_uploaded(lib, codec, dev, layout, infos, plan, total, blob, use_arena, compressed_only, timings, (t0, t1, t2))
+    return _Uploaded(dev, layout, infos, plan, total, blob, (t0, t1, t2))
 
 
 def _decode_uploaded(lib, codec, dev, layout, infos, plan, total, blob, use_arena, compressed_only, timings, marks):

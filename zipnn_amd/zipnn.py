@@ -607,6 +607,41 @@ def decompress_safetensors_tensor(tensor, device="cpu"):
 _ST_DTYPE_NAME = {"float32": "F32", "float16": "F16", "bfloat16": "BF16", "float8_e4m3fn": "F8_E4M3", "float8_e5m2": "F8_E5M2"}
 
 
+def index_rows(idx, shape, n):
+    """The index arithmetic of a slice object over a tensor of `shape` stored as `n` contiguous bytes (CompressedSlice, resident.ResidentSlice): which rows
+    [a, b) of the first dimension an index needs, as bytes [byte_lo, byte_hi) of the tensor, and the index `sel` to apply to those rows once they are decoded.
+    -> (a, b, sel, byte_lo, byte_hi, scalar)."""
+    if not isinstance(idx, tuple):
+        idx = (idx,)
+    rows = shape[0] if shape else 0
+    first, rest = (idx[0], idx[1:]) if idx else (slice(None), ())
+    a, b, lead = 0, rows, None              # decode rows [a, b); `lead` then indexes the first dimension of what was decoded
+    if not shape or rows == 0 or n == 0:
+        lead, rest = None, idx              # (a scalar or an empty tensor: nothing to range over)
+    elif isinstance(first, bool) or first is None or first is Ellipsis or not isinstance(first, (int, slice)):
+        rest = idx                          # (masks, lists, a leading Ellipsis / None: the whole tensor, the index as given)
+    elif isinstance(first, int):
+        r = first + rows if first < 0 else first
+        if not 0 <= r < rows:
+            raise IndexError(f"index {first} is out of bounds for dimension 0 with size {rows}")
+        a, b, lead = r, r + 1, 0
+    else:
+        lo, hi, step = first.indices(rows)
+        if step == 1:
+            a, b, lead = lo, max(hi, lo), slice(None)
+        elif step > 1 and hi > lo:
+            a, b, lead = lo, hi, slice(None, None, step)
+        else:
+            rest = idx                      # (negative steps: the whole tensor, torch reports what it does not index)
+    row_bytes = n // rows if rows else 0
+    byte_lo, byte_hi = a * row_bytes, b * row_bytes
+    scalar = not shape and n > 0             # a 0-dim tensor left compressed (no writer of ours or the reference's does that — the frame is larger than the
+    if scalar:                               #  value — but a third party's file may): its one element is all the bytes, decoded and viewed as the scalar (ADVICE r5)
+        byte_lo, byte_hi = 0, n
+    sel = (() if lead is None else (lead,)) + tuple(rest)
+    return a, b, sel, byte_lo, byte_hi, scalar
+
+
 class CompressedSlice:
     """`SafeOpen.get_slice(name)` of a compressed tensor: the protocol of safetensors' own slice object (`get_shape()`,
     `get_dtype()`, indexing), served by chunk-range decode.  Rows a .. b-1 of a tensor are the contiguous bytes
@@ -652,33 +687,7 @@ class CompressedSlice:
         body_off, P, bits, byts, chunk, n, tdt, shape = self._fp
         shape = tuple(int(d) for d in (shape if shape is not None else self._shape))
         work, want = self._device()
-        if not isinstance(idx, tuple):
-            idx = (idx,)
-        rows = shape[0] if shape else 0
-        first, rest = (idx[0], idx[1:]) if idx else (slice(None), ())
-        a, b, lead = 0, rows, None              # decode rows [a, b); `lead` then indexes the first dimension of what was decoded
-        if not shape or rows == 0 or n == 0:
-            lead, rest = None, idx              # (a scalar or an empty tensor: nothing to range over)
-        elif isinstance(first, bool) or first is None or first is Ellipsis or not isinstance(first, (int, slice)):
-            rest = idx                          # (masks, lists, a leading Ellipsis / None: the whole tensor, the index as given)
-        elif isinstance(first, int):
-            r = first + rows if first < 0 else first
-            if not 0 <= r < rows:
-                raise IndexError(f"index {first} is out of bounds for dimension 0 with size {rows}")
-            a, b, lead = r, r + 1, 0
-        else:
-            lo, hi, step = first.indices(rows)
-            if step == 1:
-                a, b, lead = lo, max(hi, lo), slice(None)
-            elif step > 1 and hi > lo:
-                a, b, lead = lo, hi, slice(None, None, step)
-            else:
-                rest = idx                      # (negative steps: the whole tensor, torch reports what it does not index)
-        row_bytes = n // rows if rows else 0
-        byte_lo, byte_hi = a * row_bytes, b * row_bytes
-        scalar = not shape and n > 0             # a 0-dim tensor left compressed (no writer of ours or the reference's does that — the frame is larger than the
-        if scalar:                               #  value — but a third party's file may): its one element is all the bytes, decoded and viewed as the scalar
-            byte_lo, byte_hi = 0, n
+        a, b, sel, byte_lo, byte_hi, scalar = index_rows(idx, shape, n)
         if byte_hi <= byte_lo:
             self.last_chunk_range = (0, 0)
             t = torch.empty((max(b - a, 0),) + shape[1:], dtype=tdt, device=want) if shape else torch.empty((), dtype=tdt, device=want)
@@ -694,7 +703,6 @@ class CompressedSlice:
             t = buf[byte_lo - base: byte_hi - base].view(tdt).reshape(() if scalar else (b - a,) + shape[1:])
             if want != work:
                 t = t.to(want)
-        sel = (() if lead is None else (lead,)) + tuple(rest)
         return t[sel] if sel else t
 
 
