@@ -157,6 +157,35 @@ int zn_plan_create(const zn_window_item* items, size_t count, zn_plan** plan);
 int zn_plan_run(zn_plan* plan, void* stream, int check);
 int zn_plan_destroy(zn_plan* plan);
 
+/* Decode hints: a sidecar index for bodies that STAY where they are (a resident checkpoint decodes the same streams on every forward).  huff0 has no gap
+ * array, so the fused decoder finds the start of every 64th-of-a-tile sub-block of a stream by speculation: a run-in, a check, now and then a second pass.  Those
+ * starts are the same every time.  zn_hint_build_dev decodes a body once and keeps them — one byte per sub-block of the first Huffman-coded plane of every full
+ * chunk, behind a table of one 32-bit offset per (chunk, plane) — in a device buffer of the caller's, next to the body, never inside it: frames and files are
+ * untouched.  A hinted decode starts every sub-block from its byte and checks the result exactly as it checks a guess: hints are ADVICE.  Wrong, stale or random
+ * bytes (or tables) cost time, never correctness — output bytes and the verdict are those of the unhinted call — and nothing is ever read outside
+ * [d_hints, d_hints + hint_len).
+ * VALIDITY: the tile geometry depends on the body's address modulo 4 and on this library's choice of sub-block sizes, so an index serves the body AT THE ADDRESS
+ * it had when the index was built, decoded by the library build that built it (a resident store guarantees both).  Anything else is only slower.
+ * What reads hints: the fused kernel's full-chunk workgroups in calls WITHOUT a delta base that do not take the small-input (wide) form — zn_set_decode_wide's
+ * automatic rule decides that as for any call, before hints are looked at.  Partial last chunks, further Huffman planes of a chunk, the generic path and items
+ * with a delta base (which make their whole launch unhinted) decode as they always do.
+ * zn_hint_size_dev: the index's length for the WHOLE body of `item` (chunk_lo / chunk_hi / d_dst / d_delta are ignored) — one small launch, one 8-byte read-back.
+ * zn_hint_build_dev: fills d_hints (16-byte aligned; hint_cap >= that length, else ZN_E_ARG); synchronous; device scratch: a byte per (plane, chunk).
+ * A hinted item is a window item plus its body's index (NULL / 0: none; a hint_len below zn_hint_size_dev's answer, NULL with a length, or an unaligned
+ * pointer: ZN_E_ARG — the first hinted call on a body the two functions above have not seen sizes it itself, with their read-back).  Windows index the table by
+ * the body's chunk numbers: one index serves every window of its body.  A plan made by zn_plan_create_hinted is run and destroyed like any other.
+ * (The emulated test build also exports a counter read-out with the signature (unsigned long long out[4], int reset), named like the tile counters' but with
+ * "hint" for "tile": out[0] tiles that started from hints, [1] those of them that needed a fix-up iteration, [2] tiles of hinted launches that ran without
+ * hints, [3] hint bytes written by builds.  The device build has no counters.) */
+typedef struct zn_hinted_item {
+  zn_window_item item;
+  const void* d_hints; size_t hint_len;
+} zn_hinted_item;
+int zn_hint_size_dev(const zn_window_item* item, size_t* hint_bytes, void* stream);
+int zn_hint_build_dev(const zn_window_item* item, void* d_hints, size_t hint_cap, void* stream);
+int zn_decompress_hinted_batch_dev(const zn_hinted_item* items, size_t count, void* stream, int check);
+int zn_plan_create_hinted(const zn_hinted_item* items, size_t count, zn_plan** plan);
+
 /* Delta ("byte"/"file" delta_compressed_type of the reference, zipnn/zipnn.py:625-640 and :983-1004: the bytes
  * are XORed with a second buffer of the same length before compression and after decompression).  The XOR is
  * fused into the kernels that read the tensor / write the output — no extra pass over HBM.  d_delta = NULL gives

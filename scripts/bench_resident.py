@@ -10,6 +10,10 @@ Everything timed is checked against the source bytes.  Legs:
   e  a full forward of a stack of torch.nn.Linear blocks with hook(), against the same stack with plain parameters
 Each leg runs in a child process under a time limit of its own; a leg that fails or runs out of time ends the probe.
     python scripts/bench_resident.py [--layers 4] [--out profiles/resident_decode]
+--index: the sync index instead (ResidentCheckpoint.build_index), into profiles/resident_index.{json,txt}:
+  i  per dtype (bf16, fp32, fp16, fp8 e4m3; about 1 GiB each, N(0, 0.02)): plan.run unhinted / hinted / unhinted / hinted on the same store, the build time
+     per GiB and index_bytes / nbytes
+  j  the four Llama-3-8B blocks of leg b, per block unhinted / hinted / unhinted / hinted, and leg e's hooked forward with and without the index
 """
 import argparse
 import json
@@ -22,6 +26,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 LEG_SECONDS = {"a": 240, "b": 240, "c": 300, "d": 240, "e": 300}
+INDEX_LEG_SECONDS = {"i": 420, "j": 300}
 CH = 256 * 1024
 
 
@@ -181,16 +186,152 @@ def leg_e(args):
     return res
 
 
+def _abab(store, names, scratch, reps, sd=None):
+    """plan.run of `names`: unhinted, hinted, unhinted, hinted on the SAME store (the index is built once and taken away / given back) ->
+    {"plain": [ms, ms], "hinted": [ms, ms], "kernels": …}; the A/A spread is the two plain runs'."""
+    hints = {k: store._entries[k].hints for k in names}
+    out = {"plain": [], "hinted": [], "kernels": {}}
+    for leg in ("plain", "hinted", "plain", "hinted"):
+        for k in names:
+            store._entries[k].hints = hints[k] if leg == "hinted" else None
+        plan = store.plan(names, into=scratch)
+        t = _events_ms(plan.run, reps)
+        plan.status()
+        out[leg].append(t["median_ms"])
+        out["kernels"][leg] = _capi_kernels()
+        if sd is not None:
+            for k in names:
+                assert _same(plan.tensors[k], sd[k]), (leg, k)
+        plan.close()
+    for k in names:
+        store._entries[k].hints = hints[k]
+    a, h = out["plain"], out["hinted"]
+    out["aa_spread"] = abs(a[0] - a[1]) / min(a)
+    out["gain"] = 1.0 - (sum(h) / 2) / (sum(a) / 2)
+    return out
+
+
+def _capi_kernels():
+    from zipnn_amd import _capi
+    return _capi.lib().last_kernels()
+
+
+def leg_i(args):
+    import torch
+    from zipnn_amd import ResidentCheckpoint
+    res = []
+    for name in ("bfloat16", "float32", "float16", "float8_e4m3fn"):
+        tdt = getattr(torch, name)
+        es = torch.empty(0, dtype=tdt).element_size()
+        g = torch.Generator(device="cuda"); g.manual_seed(13)
+        sd = {f"t{i}": (torch.randn((128 << 20) // es, generator=g, device="cuda") * 0.02).to(tdt) for i in range(8)}      # 8 x 128 MiB
+        store = ResidentCheckpoint.from_state_dict(sd, "cuda:0")
+        names = [k for k in sd if store.info(k)["compressed"]]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        store.build_index(all_dtypes=True)
+        torch.cuda.synchronize()
+        build_s = time.perf_counter() - t0
+        nbytes = sum(store.info(k)["nbytes"] for k in names)
+        scratch = torch.empty(store.scratch_bytes(names), dtype=torch.uint8, device="cuda")
+        r = _abab(store, names, scratch, args.reps, sd)
+        r.update(dtype=name, tensors=len(names), nbytes=nbytes, resident_bytes=store.resident_bytes, index_bytes=store.index_bytes,
+                 index_share=store.index_bytes / nbytes, build_s_per_gib=build_s / (nbytes / 2 ** 30))
+        res.append(r)
+        del store, sd, scratch
+        torch.cuda.empty_cache()
+    return {"dtypes": res}
+
+
+def leg_j(args):
+    import torch
+    from zipnn_amd import ResidentCheckpoint
+    sd, per = _blocks(args.layers)
+    store = ResidentCheckpoint.from_state_dict(sd, "cuda:0", index=True)
+    scratch = torch.empty(max(store.scratch_bytes(n) for n in per), dtype=torch.uint8, device="cuda")
+    blocks = []
+    for i, names in enumerate(per):
+        r = _abab(store, names, scratch, args.reps, sd)
+        r.update(block=i, bytes=sum(store.info(k)["nbytes"] for k in names))
+        blocks.append(r)
+    out = {"blocks": blocks, "index_bytes": store.index_bytes, "nbytes": store.nbytes}
+    del store, sd, scratch
+    # leg e's forward, hooked without and with the index
+    torch.manual_seed(5)
+    hidden, inter = 4096, 14336
+
+    class Block(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.up, self.down = torch.nn.Linear(hidden, inter, bias=False), torch.nn.Linear(inter, hidden, bias=False)
+
+        def forward(self, x):
+            return x + self.down(torch.nn.functional.silu(self.up(x)))
+    model = torch.nn.Sequential(*[Block() for _ in range(args.layers)]).to(torch.bfloat16).to("cuda").eval()
+    for p in model.parameters():
+        p.data.mul_(0.3)
+    msd = {k: v.clone() for k, v in model.state_dict().items()}
+    x = torch.randn(1, hidden, device="cuda", dtype=torch.bfloat16)
+    fw = {}
+    with torch.no_grad():
+        ref = model(x)
+        fw["plain_ms"] = _events_ms(lambda: model(x), args.reps)["median_ms"]
+        for leg in ("hooked", "hooked_index", "hooked_again", "hooked_index_again"):
+            st = ResidentCheckpoint.from_state_dict(msd, "cuda:0", index=leg.startswith("hooked_index"))
+            handle = st.hook(model)
+            assert torch.equal(model(x), ref)
+            fw[leg + "_ms"] = _events_ms(lambda: model(x), args.reps)["median_ms"]
+            fw[leg + "_kernels"] = _capi_kernels()
+            handle.status()
+            handle.remove()
+    out["forward_batch1"] = fw
+    return out
+
+
+def main_index(args):
+    results = {}
+    for leg, limit in INDEX_LEG_SECONDS.items():
+        p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--layers", str(args.layers), "--reps", str(args.reps)],
+                           capture_output=True, text=True)
+        line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+        if p.returncode != 0 or not line:
+            print(f"leg {leg} failed (exit {p.returncode}); nothing further is started\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}")
+            return 1
+        results[leg] = json.loads(line[0][7:])
+        print(f"leg {leg}: ok", flush=True)
+    out = args.out if args.out != os.path.join(ROOT, "profiles", "resident_decode") else os.path.join(ROOT, "profiles", "resident_index")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    json.dump(results, open(out + ".json", "w"), indent=1)
+    lines = ["sync index probe (ResidentCheckpoint.build_index): plan.run unhinted / hinted / unhinted / hinted on one store, device events, median ms; every result checked against its source",
+             "(i) per dtype, 8 tensors of 128 MiB, N(0, 0.02):"]
+    for r in results["i"]["dtypes"]:
+        lines.append(f"    {r['dtype']:<14} unhinted {r['plain'][0]:.4f} / {r['plain'][1]:.4f}  hinted {r['hinted'][0]:.4f} / {r['hinted'][1]:.4f}  gain {100 * r['gain']:+.1f} %  (A/A spread {100 * r['aa_spread']:.1f} %)"
+                     f"  index {r['index_bytes']} B = {100 * r['index_share']:.2f} % of the tensors, built in {r['build_s_per_gib']:.3f} s/GiB   [{r['kernels']['hinted']}]")
+    j = results["j"]
+    lines.append(f"(j) Llama-3-8B blocks (bf16), index {j['index_bytes']} B = {100 * j['index_bytes'] / j['nbytes']:.2f} %:")
+    for r in j["blocks"]:
+        lines.append(f"    block {r['block']}: unhinted {r['plain'][0]:.4f} / {r['plain'][1]:.4f}  hinted {r['hinted'][0]:.4f} / {r['hinted'][1]:.4f}  gain {100 * r['gain']:+.1f} %  (A/A spread {100 * r['aa_spread']:.1f} %)")
+    f = j["forward_batch1"]
+    lines.append(f"    forward of {args.layers} MLP blocks, batch 1: plain {f['plain_ms']:.3f} ms, hooked {f['hooked_ms']:.3f} / {f['hooked_again_ms']:.3f} ms, hooked with index {f['hooked_index_ms']:.3f} / {f['hooked_index_again_ms']:.3f} ms"
+                 f"   [{f['hooked_index_kernels']}]")
+    open(out + ".txt", "w").write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=4)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--leg", default=None)
+    ap.add_argument("--index", action="store_true", help="the sync index legs (i, j) instead of a-e")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resident_decode"))
     args = ap.parse_args()
     if args.leg:                                          # a child: one leg, its result as one JSON line
         print("RESULT " + json.dumps(globals()["leg_" + args.leg](args)))
         return 0
+    if args.index:
+        return main_index(args)
     results = {}
     for leg, limit in LEG_SECONDS.items():
         p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--layers", str(args.layers), "--reps", str(args.reps)],

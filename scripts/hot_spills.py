@@ -3,7 +3,7 @@
 inside the hot tile loop of the compile-time-D instances (between the ZN_HOT_TILE_BEGIN / ZN_HOT_TILE_END marks), i.e. on
 the path every tile takes.  A spill reload there waits on the same counter as the HBM loads in flight (s_waitcnt vmcnt)
 and costs thousands of cycles per tile; spills in the rare paths (looping form, fix-ups, tails) do not matter.
-    python scripts/hot_spills.py [-Dflag ...]
+    python scripts/hot_spills.py [-Dflag ...]          (-DZN_DECODE_HINTED_TU: the hinted instances of zn_decode_hinted.hip)
 The marks only bracket the loop body textually; blocks the compiler moved out of line (rare paths) are listed separately
 by their "looping form" neighbourhood: a scratch op counts as hot when no v_cmp/branch-to-cold label separates it — so
 read the listing it prints, not just the count."""
@@ -30,7 +30,7 @@ for i, l in enumerate(L):
     elif "ZN_HOT_TILE_END" in l and hot.get(kern) and hot[kern][-1][1] is None: hot[kern][-1][1] = i; depth = 0
     elif depth and "scratch_" in l and hot.get(kern): hot[kern][-1][2].append((i + 1, l.strip()))
 for k, v in res.items():
-    if "decode_fused" not in k: continue
+    if "decode_fused" not in k and "decode_hinted" not in k: continue      # (-DZN_DECODE_HINTED_TU: the hinted instances)
     print(k[:40], v)
     for b, e, sc in hot.get(k, []):
         print(f"   tile loop lines {b + 1}-{(e or 0) + 1}: {len(sc)} scratch ops textually inside")

@@ -18,8 +18,8 @@ fi
 g++ -O1 -g -std=c++17 -fPIC -shared -w -I. -DZN_SIMT_EMUL=1 $SAN $FILES -o libzipnn_simt.so || exit 1
 cd "$R"
 LOG="$(mktemp)"
-if [ -n "$KEXPR" ]; then LD_PRELOAD="$PRE" python -m pytest tests/test_kernels_simt.py tests/test_plugin_simt.py tests/test_legacy_weights.py tests/test_window_simt.py tests/test_resident_simt.py -x -q -k "$KEXPR" > "$LOG" 2>&1
-else LD_PRELOAD="$PRE" python -m pytest tests/test_kernels_simt.py tests/test_plugin_simt.py tests/test_legacy_weights.py tests/test_window_simt.py tests/test_resident_simt.py -x -q > "$LOG" 2>&1; fi
+if [ -n "$KEXPR" ]; then LD_PRELOAD="$PRE" python -m pytest tests/test_kernels_simt.py tests/test_plugin_simt.py tests/test_legacy_weights.py tests/test_window_simt.py tests/test_resident_simt.py tests/test_index_simt.py -x -q -k "$KEXPR" > "$LOG" 2>&1
+else LD_PRELOAD="$PRE" python -m pytest tests/test_kernels_simt.py tests/test_plugin_simt.py tests/test_legacy_weights.py tests/test_window_simt.py tests/test_resident_simt.py tests/test_index_simt.py -x -q > "$LOG" 2>&1; fi
 RC=$?
 echo "pytest rc=$RC"; tail -2 "$LOG"
 echo "sanitizer reports:"; grep -E "runtime error|ERROR: AddressSanitizer" "$LOG" | sed 's/0x[0-9a-f]*/ADDR/g' | sort | uniq -c | sort -rn | head -20

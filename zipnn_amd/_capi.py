@@ -49,6 +49,14 @@ class ZnWindowItem(ctypes.Structure):
 assert ctypes.sizeof(ZnWindowItem) == 80
 
 
+class ZnHintedItem(ctypes.Structure):
+    """struct zn_hinted_item of include/zipnn_hip.h"""
+    _fields_ = [("item", ZnWindowItem), ("d_hints", ctypes.c_void_p), ("hint_len", ctypes.c_size_t)]
+
+
+assert ctypes.sizeof(ZnHintedItem) == 96
+
+
 class ZnCBatchItem(ctypes.Structure):
     """struct zn_cbatch_item of include/zipnn_hip.h"""
     _fields_ = [("d_src", ctypes.c_void_p), ("n", ctypes.c_size_t), ("num_buf", ctypes.c_int), ("bits_mode", ctypes.c_int),
@@ -129,6 +137,14 @@ class ZnLib:
         L.zn_decompress_window_batch_dev.argtypes = [ctypes.POINTER(ZnWindowItem), sz, vp, ci]
         L.zn_plan_create.restype = ci
         L.zn_plan_create.argtypes = [ctypes.POINTER(ZnWindowItem), sz, vpp]
+        L.zn_hint_size_dev.restype = ci
+        L.zn_hint_size_dev.argtypes = [ctypes.POINTER(ZnWindowItem), ctypes.POINTER(sz), vp]
+        L.zn_hint_build_dev.restype = ci
+        L.zn_hint_build_dev.argtypes = [ctypes.POINTER(ZnWindowItem), vp, sz, vp]
+        L.zn_decompress_hinted_batch_dev.restype = ci
+        L.zn_decompress_hinted_batch_dev.argtypes = [ctypes.POINTER(ZnHintedItem), sz, vp, ci]
+        L.zn_plan_create_hinted.restype = ci
+        L.zn_plan_create_hinted.argtypes = [ctypes.POINTER(ZnHintedItem), sz, vpp]
         L.zn_plan_run.restype = ci
         L.zn_plan_run.argtypes = [vp, vp, ci]
         L.zn_plan_destroy.restype = ci
@@ -408,6 +424,43 @@ class ZnLib:
         arr, n = self._window_items(items)
         h = ctypes.c_void_p(None)
         self._check(self._L.zn_plan_create(arr, n, ctypes.byref(h)))
+        return h
+
+    # -- decode hints (include/zipnn_hip.h: a sidecar index of sub-block start positions for bodies that stay in place) --
+    @classmethod
+    def _hinted_items(cls, items):
+        """items: iterable of (window item tuple, hints_ptr or None, hint_len)."""
+        items = list(items)
+        arr = (ZnHintedItem * max(len(items), 1))()
+        for i, (win, hp, hl) in enumerate(items):
+            w, _ = cls._window_items([win])
+            arr[i].item = w[0]
+            arr[i].d_hints = hp or None
+            arr[i].hint_len = hl
+        return arr, len(items)
+
+    def hint_size_dev(self, item, stream=0):
+        """zn_hint_size_dev: bytes of the index of the whole body of `item` (a window item tuple; its window and destination are ignored)."""
+        arr, _ = self._window_items([item])
+        n = ctypes.c_size_t(0)
+        self._check(self._L.zn_hint_size_dev(arr, ctypes.byref(n), stream))
+        return int(n.value)
+
+    def hint_build_dev(self, item, hints_ptr, hint_cap, stream=0):
+        """zn_hint_build_dev: build the index of the whole body of `item` into hint_cap bytes of device memory at hints_ptr (16-byte aligned)."""
+        arr, _ = self._window_items([item])
+        self._check(self._L.zn_hint_build_dev(arr, hints_ptr, hint_cap, stream))
+
+    def decompress_hinted_batch_dev(self, items, stream=0, check=True):
+        """zn_decompress_hinted_batch_dev.  items: iterable of (window item tuple, hints_ptr or None, hint_len)."""
+        arr, n = self._hinted_items(items)
+        self._check(self._L.zn_decompress_hinted_batch_dev(arr, n, stream, 1 if check else 0))
+
+    def plan_create_hinted(self, items):
+        """zn_plan_create_hinted over items as for decompress_hinted_batch_dev -> a plan handle for plan_run / plan_destroy."""
+        arr, n = self._hinted_items(items)
+        h = ctypes.c_void_p(None)
+        self._check(self._L.zn_plan_create_hinted(arr, n, ctypes.byref(h)))
         return h
 
     def plan_run(self, plan, stream=0, check=True):

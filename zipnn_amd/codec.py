@@ -232,3 +232,18 @@ def compress_device_batch(lib, items, gap=0, return_arena=False):
     if return_arena:
         return arena, offs, lens
     return [arena[b0:b0 + n] for b0, n in zip(offs, lens)]
+
+
+def build_decode_hints(lib, items):
+    """Decode hints (include/zipnn_hip.h) for bodies that stay where they are: items = window item tuples as for
+    ZnLib.decompress_window_batch_dev (the window and the destination are ignored — an index covers the whole body).  -> one uint8 tensor
+    per item, on the body's device (a CPU tensor for the emulated library), for ZnLib.decompress_hinted_batch_dev / plan_create_hinted.
+    The hints hold for the body AT ITS ADDRESS: keep the body tensor alive and in place."""
+    out = []
+    for it in items:
+        n = lib.hint_size_dev(it)
+        dev = torch.device("cuda", current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        h = torch.empty(max(n, 16), dtype=torch.uint8, device=dev)
+        lib.hint_build_dev(it, h.data_ptr(), n)
+        out.append(h[:n])
+    return out

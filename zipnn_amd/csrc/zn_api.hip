@@ -14,6 +14,7 @@
 #include <chrono>
 #include <string>
 #include <vector>
+#include <unordered_map>
 #include <string.h>
 #include <stdlib.h>
 
@@ -266,8 +267,9 @@ static int compress_items(zn_cbatch_item* items, size_t count, hipStream_t strea
     const size_t need = nseg_all * sizeof(ZnESeg);
     if (w.h_segs_cap * sizeof(ZnSeg) < need) {
       if (w.h_segs) { ZN_HIP(hipHostFree(w.h_segs)); w.h_segs = nullptr; w.h_segs_cap = 0; }
-      ZN_HIP(hipHostMalloc((void**)&w.h_segs, need, hipHostMallocDefault));
-      w.h_segs_cap = (need + sizeof(ZnSeg) - 1) / sizeof(ZnSeg);
+      const size_t units = (need + sizeof(ZnSeg) - 1) / sizeof(ZnSeg);      // (the capacity is in whole ZnSeg: allocate what it claims, the decode calls copy by it)
+      ZN_HIP(hipHostMalloc((void**)&w.h_segs, units * sizeof(ZnSeg), hipHostMallocDefault));
+      w.h_segs_cap = units;
     }
   }
   // The one-pass encoder takes the full chunks of the call when every tensor's prefix sums fit its look-back words (40 bits)
@@ -400,6 +402,8 @@ static int zn_decode_overlap_on() {
 // geometry check, the knobs read), launched by launch_segments — once by the one-shot entry points, any number of times by a plan (zn_plan_run).
 struct DecodeSet {
   std::vector<ZnSeg> segs[3];                    // by plane count: 1, 2, 4
+  std::vector<ZnHintSeg> hsegs[3];               // a hinted call: entry i = the index of segs[q][i] (hints == null: none), else empty
+  bool hinted[3] = {false, false, false};        // … and whether any segment of the plane count has one
   uint64_t pk_of[3] = {0, 0, 0}, k_of[3] = {0, 0, 0}, wg_of[3] = {0, 0, 0}, tail_of[3] = {0, 0, 0};
   bool delta_of[3] = {false, false, false}, rest_ok[3] = {true, true, true};
   uint64_t total_chunks = 0;
@@ -414,7 +418,9 @@ static inline void zn_window_of(const zn_window_item& it, uint64_t* n, uint64_t*
   const uint64_t end = hi == kb ? (uint64_t)it.orig_size : hi * it.chunk;
   *n = end - lo * it.chunk; *k = hi - lo;
 }
-static int build_segments(const zn_window_item* items, size_t count, DecodeSet& D) {
+static int hint_size_cached(const zn_window_item& it, const ZnGeom& g, size_t* bytes);
+// hints (may be null): one entry per item
+static int build_segments(const zn_window_item* items, size_t count, DecodeSet& D, const ZnHintSeg* hints = nullptr) {
   if (count && !items) return ZN_E_ARG;
   std::vector<ZnSeg>* segs = D.segs;
   uint64_t* pk_of = D.pk_of; uint64_t* k_of = D.k_of; uint64_t* wg_of = D.wg_of; uint64_t* tail_of = D.tail_of;
@@ -445,6 +451,18 @@ static int build_segments(const zn_window_item* items, size_t count, DecodeSet& 
     int rc = check_geom(it.orig_size, it.num_buf, it.bytes_mode, it.chunk, &sg.g, it.bits_mode);      // the BODY's geometry …
     if (rc) return rc;
     if (it.chunk_lo > it.chunk_hi || it.chunk_hi > sg.g.K) return ZN_E_ARG;
+    ZnHintSeg hseg = {nullptr, 0};
+    if (hints) {
+      // an index is a pointer AND a length, 16-byte aligned, at least as long as zn_hint_size_dev says for this body
+      if ((hints[i].hints == nullptr) != (hints[i].len == 0) || (((uintptr_t)hints[i].hints) & 15u) != 0) return ZN_E_ARG;
+      if (hints[i].hints && it.d_body && it.body_len >= 9u * (size_t)sg.g.P * sg.g.K) {
+        size_t need = 0;
+        rc = hint_size_cached(it, sg.g, &need);
+        if (rc) return rc;
+        if (hints[i].len < need) return ZN_E_ARG;
+        if (!it.d_delta) hseg = hints[i];        // (a tensor with a delta base decodes without: the delta instances read no hints)
+      }
+    }
     sg.kb = (uint32_t)sg.g.K; sg.c_lo = (uint32_t)it.chunk_lo;                                        // (check_geom: P·K < 2^31)
     if (it.body_len < 9u * (size_t)sg.g.P * sg.g.K) return ZN_E_CORRUPT;
     if (it.chunk_lo == it.chunk_hi) continue;
@@ -465,6 +483,7 @@ static int build_segments(const zn_window_item* items, size_t count, DecodeSet& 
     k_of[q] += sg.g.K; pk_of[q] += (uint64_t)sg.g.P * sg.g.K; wg_of[q] += (sg.g.K + ncg - 1u) / ncg;
     if (pk_of[q] > 0x7FFFFFFFull || wg_of[q] > 0x7FFFFFFFull) return ZN_E_ARG;
     segs[q].push_back(sg);
+    if (hints) { D.hsegs[q].push_back(hseg); if (hseg.hints) D.hinted[q] = true; }
   }
   D.total_chunks = total_chunks; D.wide = wide;
   return ZN_OK;
@@ -472,7 +491,8 @@ static int build_segments(const zn_window_item* items, size_t count, DecodeSet& 
 
 // d_table: the segment table already in device memory (a plan's: 1-plane segments, then 2-, then 4-plane ones), or null — the call's own, staged through the
 // workspace's pinned buffer, which is the one thing here that makes the host wait for earlier device work.
-static int launch_segments(const DecodeSet& D, const ZnSeg* d_table, hipStream_t stream, int check) {
+// d_htable: a hinted plan's table of ZnHintSeg, parallel to d_table (a one-shot hinted call stages its own behind the segment table)
+static int launch_segments(const DecodeSet& D, const ZnSeg* d_table, hipStream_t stream, int check, const ZnHintSeg* d_htable = nullptr) {
   const std::vector<ZnSeg>* segs = D.segs;
   const uint64_t* pk_of = D.pk_of; const uint64_t* k_of = D.k_of; const uint64_t* wg_of = D.wg_of; const uint64_t* tail_of = D.tail_of;
   const bool* delta_of = D.delta_of; bool rest_ok[3] = {D.rest_ok[0], D.rest_ok[1], D.rest_ok[2]};
@@ -489,6 +509,10 @@ static int launch_segments(const DecodeSet& D, const ZnSeg* d_table, hipStream_t
   const size_t nseg_all = segs[0].size() + segs[1].size() + segs[2].size();
   const bool table = nseg_all > 1;
   const bool staged = table && !d_table;        // (the table goes through the pinned staging buffer)
+  // hinted launches: per plane count, when some segment has an index, none has a delta base and the wide kernel does not go first
+  bool use_h[3]; bool any_h = false;
+  for (int q = 0; q < 3; q++) { use_h[q] = D.hinted[q] && !wide && !delta_of[q] && D.hsegs[q].size() == segs[q].size() && !(table && d_table && !d_htable); any_h = any_h || use_h[q]; }
+  const size_t seg_units = nseg_all + (any_h ? (nseg_all * sizeof(ZnHintSeg) + sizeof(ZnSeg) - 1u) / sizeof(ZnSeg) : 0u);      // staging: the ZnHintSeg table behind the segments
   if ((rc = ws_reserve(w, WS_META_C, all_pk * sizeof(ZnPlaneDesc)))) return rc;
   if ((rc = ws_reserve(w, WS_META_B, all_k))) return rc;                     // per-chunk "done by the fused kernel" flags
   if ((rc = ws_reserve(w, WS_ENC, all_pk))) return rc;                       // … and the same per (plane, chunk)
@@ -499,11 +523,11 @@ static int launch_segments(const DecodeSet& D, const ZnSeg* d_table, hipStream_t
   if ((rc = ws_reserve(w, WS_WORDS, ZN_WORDS_BYTES))) return rc;
   if ((rc = ws_host_words(w))) return rc;
   if (staged) {
-    if ((rc = ws_reserve(w, WS_SEGS, nseg_all * sizeof(ZnSeg)))) return rc;
-    if (w.h_segs_cap < nseg_all) {
+    if ((rc = ws_reserve(w, WS_SEGS, seg_units * sizeof(ZnSeg)))) return rc;
+    if (w.h_segs_cap < seg_units) {
       if (w.h_segs) { ZN_HIP(hipHostFree(w.h_segs)); w.h_segs = nullptr; w.h_segs_cap = 0; }
-      ZN_HIP(hipHostMalloc((void**)&w.h_segs, nseg_all * sizeof(ZnSeg), hipHostMallocDefault));
-      w.h_segs_cap = nseg_all;
+      ZN_HIP(hipHostMalloc((void**)&w.h_segs, seg_units * sizeof(ZnSeg), hipHostMallocDefault));
+      w.h_segs_cap = seg_units;
     }
   }
   if ((rc = ws_acquire(w, stream))) return rc;
@@ -522,7 +546,11 @@ static int launch_segments(const DecodeSet& D, const ZnSeg* d_table, hipStream_t
     ZN_HIP(hipEventSynchronize(w.busy));
     size_t o = 0;
     for (int q = 0; q < 3; q++) for (const ZnSeg& sg : segs[q]) w.h_segs[o++] = sg;
-    ZN_HIP(hipMemcpyAsync(w.buf[WS_SEGS], w.h_segs, nseg_all * sizeof(ZnSeg), hipMemcpyHostToDevice, stream));
+    if (any_h) {
+      ZnHintSeg* hh = (ZnHintSeg*)(w.h_segs + nseg_all); size_t oh = 0;
+      for (int q = 0; q < 3; q++) for (size_t i = 0; i < segs[q].size(); i++) hh[oh++] = use_h[q] ? D.hsegs[q][i] : ZnHintSeg{nullptr, 0};
+    }
+    ZN_HIP(hipMemcpyAsync(w.buf[WS_SEGS], w.h_segs, seg_units * sizeof(ZnSeg), hipMemcpyHostToDevice, stream));
   }
   size_t seg_base = 0; uint64_t k_base = 0, pk_base = 0, tail_base = 0;
   const hipStream_t stream_main = stream;
@@ -567,6 +595,14 @@ static int launch_segments(const DecodeSet& D, const ZnSeg* d_table, hipStream_t
     //  generic launches behind it, and the generic merge of ONE partial chunk takes 33 µs: 1 GiB + 200 KB 445 µs that way, 417 this way; 4 GiB + 200 KB 1 573 / 1 555.
     //  From about 6 GiB on the percent outweighs the 33 µs: the Llama-3-8B batch — 16 GB of bf16, its 8 KB norm vectors the partial chunks — 12.12 ms against 11.94)
     if (total_chunks > ZN_REST_MAX_CHUNKS && (tail_of[q] == 0 || k_of[q] > ZN_REST_TAIL_MAX_CHUNKS)) rest_ok[q] = false;
+    if (use_h[q]) {
+      // (the plain instance's place: tail workgroups at the front, the generic launches behind it)
+      const ZnHintSeg* d_hsegs = table ? (d_table ? d_htable : (const ZnHintSeg*)((const ZnSeg*)w.buf[WS_SEGS] + nseg_all)) + seg_base : nullptr;
+      zn_launch_decode_hinted(P, 1, segs[q][0], d_segs, nseg, D.hsegs[q][0], d_hsegs, (uint32_t)wg_of[q], d_done, d_pdone, d_status, (uint32_t)tail_of[q], d_tails, d_tail_done, stream);
+      zn_launch_decode_generic(P, segs[q][0], d_segs, nseg, pk_of[q], k_of[q], d_descs, d_status, d_done, d_pdone, d_tails, d_tail_done, stream);
+      status_zeroed = true;
+      continue;
+    }
     const bool rest = zn_launch_decode_fused(P, segs[q][0], d_segs, nseg, (uint32_t)wg_of[q], d_done, d_pdone, d_status, (uint32_t)tail_of[q], d_tails,
                                              d_tail_done, delta_of[q], wide, status_zeroed, rest_ok[q] ? d_descs : nullptr,
                                              tail_of[q] ? (uint32_t*)((uint8_t*)w.buf[WS_META_A] + sync_off) + 2u * tail_base : nullptr, stream);
@@ -598,6 +634,133 @@ static int launch_segments(const DecodeSet& D, const ZnSeg* d_table, hipStream_t
     if (st & ZN_DEV_SYNC_TIMEOUT) { t_hip_err = "a workgroup gave up waiting for another one of the same launch (device preempted or faulted?)"; return ZN_E_TIMEOUT; }
   }
   return ZN_OK;
+}
+
+// ---- decode hints ----
+// The sizing pass over one whole body: *bytes = the length of its index (offset table + hint bytes); d_offs (may be null) receives the table.  One launch and
+// one 8-byte read-back; takes the device's workspace lock.
+static int hint_size_run(const zn_window_item& it, const ZnGeom& g, uint32_t* d_offs, size_t* bytes, hipStream_t stream) {
+  int dev = 0;
+  ZN_HIP(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) return ZN_E_ARG;
+  std::lock_guard<std::mutex> lk(g_dev_mu[dev]);
+  Workspace& w = g_ws[dev];
+  int rc;
+  if ((rc = ws_reserve(w, WS_TOTALS, 64))) return rc;
+  if ((rc = ws_host_words(w))) return rc;
+  if ((rc = ws_acquire(w, stream))) return rc;
+  zn_launch_hint_size(g, (const uint8_t*)it.d_body, it.body_len, d_offs, (uint64_t*)w.buf[WS_TOTALS], stream);
+  { const hipError_t el = hipGetLastError(); if (el != hipSuccess) { t_hip_err = std::string("kernel launch: ") + hipGetErrorString(el); (void)ws_release(w, stream); return ZN_E_HIP; } }
+  ZN_HIP(hipMemcpyAsync(w.h_total, w.buf[WS_TOTALS], sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  if ((rc = ws_release(w, stream))) return rc;
+  ZN_HIP(hipStreamSynchronize(stream));
+  const uint64_t total = *w.h_total;
+  if (total > 0xFFFFFFFFull) return ZN_E_ARG;      // (the table's offsets are 32 bits: a body of hundreds of GiB)
+  *bytes = (size_t)total;
+  return ZN_OK;
+}
+// What the hinted entry points hold a caller's hint_len against: the sizes zn_hint_size_dev / zn_hint_build_dev have worked out, remembered per body (address,
+// length, geometry); a body they have not seen is sized on the spot (a read-back: once per body).  Only an argument check — the kernels hold every read of an
+// index against the length they are given, whatever this says.
+struct HintKey { const void* body; size_t body_len, n, chunk; int P; bool operator==(const HintKey& o) const { return body == o.body && body_len == o.body_len && n == o.n && chunk == o.chunk && P == o.P; } };
+struct HintKeyHash { size_t operator()(const HintKey& k) const { return std::hash<const void*>()(k.body) ^ (k.body_len * 0x9E3779B97F4A7C15ull) ^ (k.n << 1) ^ (size_t)k.P; } };
+static std::mutex g_hint_mu;
+static std::unordered_map<HintKey, size_t, HintKeyHash> g_hint_sizes;
+static void hint_size_remember(const zn_window_item& it, const ZnGeom& g, size_t bytes) {
+  std::lock_guard<std::mutex> lk(g_hint_mu);
+  if (g_hint_sizes.size() > (1u << 20)) g_hint_sizes.clear();
+  g_hint_sizes[HintKey{it.d_body, it.body_len, it.orig_size, it.chunk, (int)g.P}] = bytes;
+}
+static int hint_size_cached(const zn_window_item& it, const ZnGeom& g, size_t* bytes) {
+  {
+    std::lock_guard<std::mutex> lk(g_hint_mu);
+    auto f = g_hint_sizes.find(HintKey{it.d_body, it.body_len, it.orig_size, it.chunk, (int)g.P});
+    if (f != g_hint_sizes.end()) { *bytes = f->second; return ZN_OK; }
+  }
+  const int rc = hint_size_run(it, g, nullptr, bytes, nullptr);
+  if (rc == ZN_OK) hint_size_remember(it, g, *bytes);
+  return rc;
+}
+static int hint_item_geom(const zn_window_item* it, ZnGeom* g) {
+  if (!it || !it->d_body) return ZN_E_ARG;
+  const int rc = check_geom(it->orig_size, it->num_buf, it->bytes_mode, it->chunk, g, it->bits_mode);
+  if (rc) return rc;
+  if (it->body_len < 9u * (size_t)g->P * g->K) return ZN_E_CORRUPT;
+  return ZN_OK;
+}
+
+int zn_hint_size_dev(const zn_window_item* item, size_t* hint_bytes, void* stream_) {
+  if (!hint_bytes) return ZN_E_ARG;
+  *hint_bytes = 0;
+  try {
+    ZnGeom g;
+    int rc = hint_item_geom(item, &g);
+    if (rc) return rc;
+    t_kernels.clear();
+    rc = hint_size_run(*item, g, nullptr, hint_bytes, (hipStream_t)stream_);
+    if (rc == ZN_OK) hint_size_remember(*item, g, *hint_bytes);
+    return rc;
+  } catch (...) { return ZN_E_ALLOC; }
+}
+
+int zn_hint_build_dev(const zn_window_item* item, void* d_hints, size_t hint_cap, void* stream_) {
+  try {
+    ZnGeom g;
+    int rc = hint_item_geom(item, &g);
+    if (rc) return rc;
+    if (!d_hints || (((uintptr_t)d_hints) & 15u) != 0 || hint_cap < zn_hint_header_bytes_host((uint64_t)g.P * g.K)) return ZN_E_ARG;
+    hipStream_t stream = (hipStream_t)stream_;
+    t_kernels.clear();
+    // the table first (it is the head of the buffer: what fits the smallest legal capacity), and with it the size the bytes need
+    size_t need = 0;
+    rc = hint_size_run(*item, g, (uint32_t*)d_hints, &need, stream);
+    if (rc) return rc;
+    hint_size_remember(*item, g, need);
+    if (hint_cap < need) return ZN_E_ARG;
+    if (g.K == 0) return ZN_OK;
+    int dev = 0;
+    ZN_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64) return ZN_E_ARG;
+    std::lock_guard<std::mutex> lk(g_dev_mu[dev]);
+    Workspace& w = g_ws[dev];
+    const uint64_t pk = (uint64_t)g.P * g.K;
+    if ((rc = ws_reserve(w, WS_META_B, g.K))) return rc;
+    if ((rc = ws_reserve(w, WS_ENC, pk))) return rc;
+    if ((rc = ws_reserve(w, WS_WORDS, ZN_WORDS_BYTES))) return rc;
+    if ((rc = ws_acquire(w, stream))) return rc;
+    // (hint bytes of tiles the build does not reach — chunks it declines, slack of the tile bound — are zero: deterministic, and as good a guess as any)
+    ZN_HIP(hipMemsetAsync((uint8_t*)d_hints + zn_hint_header_bytes_host(pk), 0, need - zn_hint_header_bytes_host(pk), stream));
+    ZnSeg sg;
+    sg.g = g; sg.body = (const uint8_t*)item->d_body; sg.body_len = item->body_len; sg.dst = nullptr;
+    sg.chunk0 = 0; sg.kb = (uint32_t)g.K; sg.desc0 = 0; sg.c_lo = 0; sg.wg0 = 0; sg.ncg = zn_decode_fused_group(g.K);
+    sg.tail0 = 0; sg.has_tail = (g.n % g.chunk) != 0 ? 1u : 0u; sg.xr = nullptr;
+    // (the status words of a build are the first 16 bytes of the words buffer — no decode slot: a damaged body builds hints of whatever it holds, and the decode says so)
+    uint32_t* d_status = (uint32_t*)w.buf[WS_WORDS];
+    ZN_HIP(hipMemsetAsync(d_status, 0, 4 * sizeof(uint32_t), stream));
+    const ZnHintSeg hs = {(uint8_t*)d_hints, (uint64_t)need};
+    zn_launch_decode_hinted((int)g.P, 2, sg, nullptr, 1, hs, nullptr, (uint32_t)((g.K + sg.ncg - 1u) / sg.ncg), (uint8_t*)w.buf[WS_META_B], (uint8_t*)w.buf[WS_ENC], d_status, 0, nullptr, nullptr, stream);
+    { const hipError_t el = hipGetLastError(); if (el != hipSuccess) { t_hip_err = std::string("kernel launch: ") + hipGetErrorString(el); (void)ws_release(w, stream); return ZN_E_HIP; } }
+    if ((rc = ws_release(w, stream))) return rc;
+    ZN_HIP(hipStreamSynchronize(stream));
+    return ZN_OK;
+  } catch (...) { return ZN_E_ALLOC; }
+}
+
+static int split_hinted(const zn_hinted_item* items, size_t count, std::vector<zn_window_item>& win, std::vector<ZnHintSeg>& hs) {
+  if (count && !items) return ZN_E_ARG;
+  win.resize(count); hs.resize(count);
+  for (size_t i = 0; i < count; i++) { win[i] = items[i].item; hs[i].hints = (uint8_t*)items[i].d_hints; hs[i].len = items[i].hint_len; }
+  return ZN_OK;
+}
+int zn_decompress_hinted_batch_dev(const zn_hinted_item* items, size_t count, void* stream_, int check) {
+  try {
+    std::vector<zn_window_item> win; std::vector<ZnHintSeg> hs;
+    int rc = split_hinted(items, count, win, hs);
+    if (rc) return rc;
+    DecodeSet D;
+    rc = build_segments(win.data(), count, D, hs.data());
+    return rc ? rc : launch_segments(D, nullptr, (hipStream_t)stream_, check);
+  } catch (...) { return ZN_E_ALLOC; }
 }
 
 static inline zn_window_item zn_whole_window(const zn_batch_item& it) {      // the window [0, K): the whole tensor
@@ -649,6 +812,7 @@ int zn_decompress_window_batch_dev(const zn_window_item* items, size_t count, vo
 struct zn_plan {
   DecodeSet D;
   ZnSeg* d_table = nullptr;      // 1-plane segments, then 2-, then 4-plane ones (null: at most one segment, which travels as a kernel argument)
+  ZnHintSeg* d_htable = nullptr; // a hinted plan: the segments' indexes, in the same order (behind the segments, in the same allocation)
   hipEvent_t last = nullptr;     // recorded behind every run: what zn_plan_destroy waits for (no stream handle is kept — see ws_acquire)
   bool ran = false;
   int dev = 0;
@@ -659,7 +823,18 @@ struct zn_plan {
 };
 extern "C" {
 
-int zn_plan_create(const zn_window_item* items, size_t count, zn_plan** plan) {
+static int plan_create(const zn_window_item* items, size_t count, const ZnHintSeg* hints, zn_plan** plan);
+int zn_plan_create(const zn_window_item* items, size_t count, zn_plan** plan) { return plan_create(items, count, nullptr, plan); }
+int zn_plan_create_hinted(const zn_hinted_item* items, size_t count, zn_plan** plan) {
+  if (!plan) return ZN_E_ARG;
+  *plan = nullptr;
+  try {
+    std::vector<zn_window_item> win; std::vector<ZnHintSeg> hs;
+    const int rc = split_hinted(items, count, win, hs);
+    return rc ? rc : plan_create(win.data(), count, hs.data(), plan);
+  } catch (...) { return ZN_E_ALLOC; }
+}
+static int plan_create(const zn_window_item* items, size_t count, const ZnHintSeg* hints, zn_plan** plan) {
   if (!plan) return ZN_E_ARG;
   *plan = nullptr;
   try {
@@ -668,14 +843,21 @@ int zn_plan_create(const zn_window_item* items, size_t count, zn_plan** plan) {
     if (dev < 0 || dev >= 64) return ZN_E_ARG;
     std::unique_ptr<zn_plan> pl(new zn_plan());          // (whatever throws or fails below takes the plan, its table and its event with it)
     pl->dev = dev;
-    const int rc = build_segments(items, count, pl->D);
+    const int rc = build_segments(items, count, pl->D, hints);
     if (rc) return rc;
     std::vector<ZnSeg> all;
     for (int q = 0; q < 3; q++) all.insert(all.end(), pl->D.segs[q].begin(), pl->D.segs[q].end());
+    std::vector<ZnHintSeg> allh;
+    if (pl->D.hinted[0] || pl->D.hinted[1] || pl->D.hinted[2])
+      for (int q = 0; q < 3; q++) for (size_t i = 0; i < pl->D.segs[q].size(); i++) allh.push_back(i < pl->D.hsegs[q].size() ? pl->D.hsegs[q][i] : ZnHintSeg{nullptr, 0});
     if (all.size() > 1) {
-      hipError_t e = hipMalloc((void**)&pl->d_table, all.size() * sizeof(ZnSeg));
+      hipError_t e = hipMalloc((void**)&pl->d_table, all.size() * sizeof(ZnSeg) + allh.size() * sizeof(ZnHintSeg));
       if (e != hipSuccess) { pl->d_table = nullptr; t_hip_err = std::string("hipMalloc: ") + hipGetErrorString(e); (void)hipGetLastError(); return ZN_E_ALLOC; }
       ZN_HIP(hipMemcpy(pl->d_table, all.data(), all.size() * sizeof(ZnSeg), hipMemcpyHostToDevice));
+      if (!allh.empty()) {
+        pl->d_htable = (ZnHintSeg*)(pl->d_table + all.size());
+        ZN_HIP(hipMemcpy(pl->d_htable, allh.data(), allh.size() * sizeof(ZnHintSeg), hipMemcpyHostToDevice));
+      }
     }
     ZN_HIP(hipEventCreateWithFlags(&pl->last, hipEventDisableTiming));
     *plan = pl.release();
@@ -689,7 +871,7 @@ int zn_plan_run(zn_plan* plan, void* stream_, int check) {
     int dev = 0;
     ZN_HIP(hipGetDevice(&dev));
     if (dev != plan->dev) return ZN_E_ARG;       // (the table and everything it points to live on the device the plan was made on)
-    const int rc = launch_segments(plan->D, plan->d_table, (hipStream_t)stream_, check);
+    const int rc = launch_segments(plan->D, plan->d_table, (hipStream_t)stream_, check, plan->d_htable);
     // (also behind a run that failed part-way: some of its kernels may be queued and read the table)
     if (plan->d_table) { if (hipEventRecord(plan->last, (hipStream_t)stream_) == hipSuccess) plan->ran = true; else { (void)hipGetLastError(); (void)hipDeviceSynchronize(); } }
     return rc;

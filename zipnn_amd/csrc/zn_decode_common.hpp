@@ -13,7 +13,7 @@
 template <int KEY>
 __device__ __forceinline__ uint64_t zn_seg_key(const ZnSeg& s) { return KEY == 0 ? (uint64_t)s.wg0 : KEY == 1 ? (uint64_t)s.desc0 : KEY == 2 ? (uint64_t)s.chunk0 : (uint64_t)s.tail0; }
 template <int KEY>
-__device__ __forceinline__ ZnSeg zn_find_seg(const ZnSeg& one, const ZnSeg* __restrict__ segs, uint32_t nseg, uint64_t b) {
+__device__ __forceinline__ ZnSeg zn_find_seg(const ZnSeg& one, const ZnSeg* __restrict__ segs, uint32_t nseg, uint64_t b, uint32_t* idx = nullptr) {
   // (a struct VALUE that is overwritten, not a choice between two struct ADDRESSES: returning `one` or `segs[lo]` made the compiler keep the
   //  by-value kernel argument in private memory — every thread of every workgroup wrote its 96 bytes to scratch and read them back: 24 KB per
   //  workgroup of the fused kernel, 96 KB per workgroup of the wide one, +37 % HBM writes on a 64 MiB decode; profiles/r04_decode_experiments.txt)
@@ -22,6 +22,7 @@ __device__ __forceinline__ ZnSeg zn_find_seg(const ZnSeg& one, const ZnSeg* __re
     uint32_t lo = 0, hi = nseg;               // invariant: key(lo) ≤ b, key(hi) > b (hi == nseg: past the end)
     while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (zn_seg_key<KEY>(segs[mid]) <= b) lo = mid; else hi = mid; }
     r = segs[lo];
+    if (idx) *idx = lo;                       // (the hinted kernels: the segment's entry in the table parallel to segs)
   }
   return r;
 }

@@ -121,12 +121,25 @@ __device__ __forceinline__ uint32_t zn_bfi_(uint32_t mask, uint32_t a, uint32_t 
 
 // path counters of the emulated build (tests/simt): which form decoded how many tiles — [0] tiles, [1] looping form,
 // [2] fix-up iterations, [3] tiles written in several lane groups.  The device build has none of this.
-#if defined(ZN_SIMT_EMULATOR)
-static unsigned long long zn_dbg_tiles[8];
+#if defined(ZN_SIMT_EMULATOR) && defined(ZN_DECODE_HINTED_TU)
+extern unsigned long long zn_dbg_tiles[8], zn_dbg_hint[4];      // (this unit's tiles count with the other one's)
+#define ZN_DBG_COUNT(i) do { if (lane == 0) zn_dbg_tiles[i]++; } while (0)
+#define ZN_HINT_COUNT(i, n) do { if (lane == 0) zn_dbg_hint[i] += (n); } while (0)
+#define ZN_HINT_FIXUP() do { if (hinted && !hfix) { hfix = true; ZN_HINT_COUNT(1, 1); } } while (0)
+#elif defined(ZN_SIMT_EMULATOR)
+unsigned long long zn_dbg_tiles[8];
 extern "C" void zn_debug_tile_counters(unsigned long long* out, int reset) { for (int i = 0; i < 8; i++) { out[i] = zn_dbg_tiles[i]; if (reset) zn_dbg_tiles[i] = 0; } }
 #define ZN_DBG_COUNT(i) do { if (lane == 0) zn_dbg_tiles[i]++; } while (0)
+// … and of the hinted forms: [0] tiles that started from hints, [1] those of them that needed a fix-up iteration (either form), [2] tiles of
+// hinted launches that ran without hints, [3] hint bytes written by builds
+unsigned long long zn_dbg_hint[4];
+extern "C" void zn_debug_hint_counters(unsigned long long* out, int reset) { for (int i = 0; i < 4; i++) { out[i] = zn_dbg_hint[i]; if (reset) zn_dbg_hint[i] = 0; } }
+#define ZN_HINT_COUNT(i, n) do { if (lane == 0) zn_dbg_hint[i] += (n); } while (0)
+#define ZN_HINT_FIXUP() do { if (hinted && !hfix) { hfix = true; ZN_HINT_COUNT(1, 1); } } while (0)
 #else
 #define ZN_DBG_COUNT(i) do { } while (0)
+#define ZN_HINT_COUNT(i, n) do { } while (0)
+#define ZN_HINT_FIXUP() do { } while (0)
 #endif
 
 // stream-tile dword i lives at in[ZN_IN_IDX(i)] (a padded layout — one dword per 32 against the 4-way bank conflict of the D = 4 refills —
@@ -169,6 +182,19 @@ typedef uint32_t __attribute__((aligned(1))) zn_u32u;
 #else
 #define ZN_ST128_4(p, a, b, c, d) ZN_ST128(p, a, b, c, d)
 #endif
+
+// ---- decode hints: the layout both the sizing pass and the hinted decoders compute ----
+__device__ __forceinline__ uint64_t zn_hint_header_bytes(uint64_t pk) { return ((pk + 1u) * 4u + 63u) & ~63ull; }      // (== zn_hint_header_bytes_host)
+// hint bytes of one huff0 stream of `slen` bytes that decodes to `seg` symbols (unit: symbols per flushed row): 64 per tile, for as many tiles as the stream has at
+// the SMALLEST sub-block size the decoder can choose for it — its density rule's value before the dense-code instance raises it to ZN_F_DCONST2, capped at
+// ZN_F_DCAP whether or not the cap applies — and at the worst alignment (three bytes into a dword).  A function of the jump table alone, so the four streams'
+// places inside a plane's region do not depend on where the body lies; what depends on the address (tile boundaries: gdw = stream - mis) is the bytes' content.
+__device__ __forceinline__ uint32_t zn_hint_stream_bytes(uint32_t slen, uint32_t seg, uint32_t unit) {
+  uint32_t d = ((ZN_F_RING_BYTES - unit - 128u) * slen) / (256u * seg);
+  d = d > ZN_F_DCAP ? ZN_F_DCAP : (d < 1u ? 1u : d);
+  const uint32_t dw = (slen + 6u) >> 2, td = 64u * d;
+  return 64u * ((dw + td - 1u) / td);
+}
 
 struct ZnFusedPlane { uint64_t off; uint32_t kind; uint32_t csize; };   // off: body offset (RAW/HUF) or byte value (RLE)
 
@@ -233,11 +259,16 @@ __device__ __forceinline__ void zn_fused_fill_luts(LDS& L, uint32_t tid, uint32_
 // which lets the tile loads / staging loops unroll exactly), 0 = run-time Du.
 // X: the output is XORed with the delta base `xq` (same offsets as outq; may still be null for a tensor without one).
 // xq == outq accumulates into rows already written (every row is loaded before it is stored, once).
-template <int P, int H, int DC, bool X = false>
+// HM: decode hints — 0: none; 1: `hq_` holds one byte per sub-block of this stream (tile t from the stream's top, lane k: hq_[64 t + k], `hcap_` bytes),
+// the distance g of the lane's start below the top of its sub-block, which takes the place of the sync run-in.  It is advice: masked to 0..10, checked by the chain
+// like a guess, and a null hq_ decodes as HM 0 does.  2: the same decode WRITES those bytes once a tile's chain has closed, and its flush neither loads raw planes
+// nor stores rows (the build of an index needs no destination).
+template <int P, int H, int DC, bool X = false, int HM = 0>
 __device__ __forceinline__ bool zn_fused_wave(const ZnGeom& g, const uint8_t* __restrict__ body, const uint8_t* body_end,
                                               uint8_t* outq_, const uint8_t* xq_, const ZnFusedPlane (&pl_)[P], const uint8_t* const (&rawq_)[P],
                                               const uint2* lut, uint32_t* ring, uint32_t* in, uint32_t lane_, uint32_t seg_,
-                                              uint32_t TL_, uint32_t Du, const uint8_t* stream_, uint32_t slen_, bool ragged ZN_PT_PARAM) {
+                                              uint32_t TL_, uint32_t Du, const uint8_t* stream_, uint32_t slen_, bool ragged ZN_PT_PARAM,
+                                              uint8_t* hq_ = nullptr, uint32_t hcap_ = 0) {
   // Everything the caller hands over is the same in all 64 lanes, but most of it came through LDS or was derived from
   // threadIdx, which makes it per-lane data to the compiler: vector registers, and exec-masked control flow around every
   // branch that depends on it (the tile loop, the choice of the decode form).  Say that it is uniform.
@@ -253,6 +284,9 @@ __device__ __forceinline__ bool zn_fused_wave(const ZnGeom& g, const uint8_t* __
   constexpr int EPL = (P == 1) ? 16 : 8;      // bytes per plane per lane in one flushed row
   constexpr int EW = EPL / 4;                 // … in dwords
   constexpr uint32_t UNIT = 64u * EPL;        // symbols per flushed row (lane row = EPL*P output bytes)
+  uint8_t* const hq = HM ? zn_uniform_ptr(hq_) : nullptr; const uint32_t hcap = HM ? zn_uniform(hcap_) : 0u;
+  const bool hinted = (HM == 1) && hq != nullptr;      // (wave-uniform)
+  uint32_t ht = 0, hb_nx = 0;                 // HM: the tile's index from the stream's top; HM 1: the NEXT tile's hint byte of this lane (requested with the tile prefetch)
   // rows kept in registers at once (fetched before the write pass, emitted after it).  A 4-plane row holds three
   // raw planes in registers: two rows at a time, or the kernel spills (ZN_F_RB4).
 #define ZN_F_RB4 2
@@ -285,6 +319,7 @@ __device__ __forceinline__ bool zn_fused_wave(const ZnGeom& g, const uint8_t* __
   // registers per stream / plane / output, and then spilled them and reloaded them behind an s_waitcnt vmcnt(0)
   uint32_t lane_v = lane;
   auto fetch_row_to = [&](uint32_t (&pre)[RB][P][EW], uint32_t first_row_sym, int r) {
+    if constexpr (HM == 2) return;             // (the hint-writing form stores no rows: it needs no raw bytes)
     for (int p = 0; p < P; p++) if (p != H && pl[p].kind == ZN_KIND_RAW) {
       // (a wave-uniform base + a 32-bit lane offset: the compiler then addresses with a scalar base register and one vector
       //  offset instead of keeping — and spilling — a 64-bit pointer per lane and row)
@@ -347,6 +382,7 @@ __device__ __forceinline__ bool zn_fused_wave(const ZnGeom& g, const uint8_t* __
           pre[r][(P >= 2) ? P - 2 : 0][k] = ZN_BFI(0x7F7F7F7Fu, lo, hi << 7);
         }
     }
+    if constexpr (HM != 2)
     for (int r = 0; r < RB; r++) if (r < nrows) {
       if (X && r % XG == 0 && r + XG < RB) load_delta(r / XG + 1);
       const uint32_t* xr_ = xd[(r / XG) & 1][r % XG];
@@ -379,6 +415,7 @@ __device__ __forceinline__ bool zn_fused_wave(const ZnGeom& g, const uint8_t* __
 
   uint32_t JF = 0;                            // symbols flushed to HBM so far
   if (H < 0) {
+    if constexpr (HM == 2) return true;
     // no Huffman plane: the chunk is a pure P-way interleave of raw / RLE planes
     while (JF < seg) {
       const uint32_t left = (seg - JF) / UNIT; const int nr = left < (uint32_t)RB ? (int)left : RB;
@@ -442,6 +479,12 @@ __device__ __forceinline__ bool zn_fused_wave(const ZnGeom& g, const uint8_t* __
     if (lane == 0) in[ZN_IN_IDX(TD)] = nx_last;
     __builtin_amdgcn_wave_barrier();
   };
+  // HM 1: tile t's 64 hint bytes, one coalesced byte load per wave, requested AHEAD of the stream tile's dwords (the loads return in order: the wait
+  // for the staged tile — the flush's one wait — covers it) and kept in one register until the top of that tile
+  auto fetch_hint = [&](uint32_t t) {
+    if constexpr (HM == 1) { hb_nx = 0; if (hinted && 64u * t + 64u <= hcap) hb_nx = hq[64u * t + lane_v]; }
+  };
+  fetch_hint(0);
   fetch_tile(hi_dw - TD, hi_dw);
   stage_tile();
 
@@ -500,7 +543,8 @@ __device__ __forceinline__ bool zn_fused_wave(const ZnGeom& g, const uint8_t* __
     J = zn_uniform(J); JF = zn_uniform(JF);
     // ---- tile: dwords [lo_dw, hi_dw) of the stream, plus one below for look-ahead ----
     const int32_t lo_dw = hi_dw - TD;
-    if (32 * lo_dw > b0) fetch_tile(lo_dw - TD, lo_dw);      // prefetch the next tile while this one is decoded
+    const uint32_t hb = hb_nx, ht_cur = ht; ht++;
+    if (32 * lo_dw > b0) { fetch_hint(ht); fetch_tile(lo_dw - TD, lo_dw); }      // prefetch the next tile while this one is decoded
     // (tried, r02: requesting the rows this tile will PROBABLY complete — predicted from the previous tile's count — at the top of
     //  the tile, a whole decode pass ahead: no gain; a second flush batch's rows requested behind the first batch's wait: slower)
     // (tried, r02: touching the raw-plane lines this tile's flush will need — one dword per 128-byte line, at the top of
@@ -513,6 +557,21 @@ __device__ __forceinline__ bool zn_fused_wave(const ZnGeom& g, const uint8_t* __
     const bool regular = (32 * lo_dw >= b0);             // every lane owns a whole sub-block (stop == lo_k, all active)
     ZN_PT_COUNT(18, 1);                      // tiles
     ZN_DBG_COUNT(0);
+    if (HM == 1) { if (hinted) ZN_HINT_COUNT(0, 1); else ZN_HINT_COUNT(2, 1); }
+    bool hfix = false; (void)hfix;           // (emulated build: this tile has been counted as one whose hints needed a fix-up)
+    // the hinted start: g = the byte, masked and clamped to what a start can be (a code is at most 11 bits long), and never below the sub-block's own end —
+    // whatever the byte holds, the lane starts inside its own sub-block, as a guess that the chain check below verifies
+    auto hint_start = [&]() -> int32_t {
+      const uint32_t g4 = hb & 15u; const int32_t gg = (int32_t)(g4 > 10u ? 10u : g4);
+      const int32_t sh_ = hi_k - gg;
+      return (lane > 0) ? (active ? (sh_ > stop ? sh_ : stop) : hi_k) : carry;      // (active: stop < hi_k)
+    };
+    // (the closed chain's starts, for the hint-writing form)
+    auto hint_store = [&](int32_t s_final) {
+      if constexpr (HM == 2) {
+        if (hq && 64u * ht_cur + 64u <= hcap) { hq[64u * ht_cur + lane_v] = (uint8_t)((lane > 0 && active) ? ((uint32_t)(hi_k - s_final) & 15u) : 0u); ZN_HINT_COUNT(3, 64); }
+      }
+    };
 
     // ---- the register-resident form (zn_decode_chain.hpp): decode once, verify the chain, compact, flush.  It commits
     // nothing before it knows that the tile is its own; what it does not take — more than TF whole-group steps in some
@@ -522,7 +581,8 @@ __device__ __forceinline__ bool zn_fused_wave(const ZnGeom& g, const uint8_t* __
     if (TF > 0) {
       ZN_PRIO(ZN_F_PRIO_SYNC);
       if (DC) ZN_ASM_MARK("ZN_MARK sync");
-      int32_t s = sync_run(base_bit, hi_k, active, regular);
+      int32_t s;
+      if (HM == 1 && hinted) s = hint_start(); else s = sync_run(base_bit, hi_k, active, regular);
       ZN_PRIO(ZN_F_PRIO_COUNT);
       ZN_PT(5);   // sync run-in
       if (DC) ZN_ASM_MARK("ZN_MARK pass1");
@@ -543,7 +603,8 @@ __device__ __forceinline__ bool zn_fused_wave(const ZnGeom& g, const uint8_t* __
         ZN_PT_COUNT(16, 1);                    // number of fix-up iterations
         ZN_PT_COUNT(17, __popcll(__ballot(mism)));
         ZN_DBG_COUNT(2);
-        if (it == 0) note_mismatch();
+        ZN_HINT_FIXUP();
+        if (it == 0 && !(HM == 1 && hinted)) note_mismatch();      // (a hinted stream has no run-in to lengthen)
         if (mism) s = e_prev;                  // (every lane decodes again: the lanes run in lock-step anyway; round 5 tried the mismatching lanes alone, exec-masked,
                                                //  for the dense instance: fp8 1.354 vs 1.202 ms, fp16 0.576 vs 0.559 — the masks cost more than the conflict-free look-ups save)
       }
@@ -559,6 +620,7 @@ __device__ __forceinline__ bool zn_fused_wave(const ZnGeom& g, const uint8_t* __
         if (J + N <= seg && base + N <= ZN_F_RING_BYTES - 4u) {
           const uint32_t nact = (uint32_t)__popcll(__ballot(active));
           carry = __builtin_amdgcn_readlane(e, (int)(nact ? nact - 1u : 0u)); hi_dw = lo_dw;
+          hint_store(s);
           // rows that will be complete after this tile: request their raw bytes now, use them after the compaction
           int rows = (int)zn_uniform((base + N) / UNIT);
           const uint32_t total_rows = (uint32_t)rows;
@@ -605,7 +667,8 @@ __device__ __forceinline__ bool zn_fused_wave(const ZnGeom& g, const uint8_t* __
       ZN_PT_COUNT(22, 1);                    // tiles that took the looping form
       ZN_DBG_COUNT(1);
       ZN_PRIO(ZN_F_PRIO_SYNC);
-      int32_t s = sync_run(base_bit, hi_k, active, regular);
+      int32_t s;
+      if (HM == 1 && hinted) s = hint_start(); else s = sync_run(base_bit, hi_k, active, regular);
       ZN_PRIO(ZN_F_PRIO_COUNT);
       ZnChain A; A.wpos = 0;
       // (whole-group steps no lane of a regular tile can take too far: see zn_fused_run)
@@ -618,7 +681,8 @@ __device__ __forceinline__ bool zn_fused_wave(const ZnGeom& g, const uint8_t* __
         const int32_t e_prev = __shfl_up(e, 1u);
         const bool mism = active && lane > 0 && e_prev != s;
         if (!__any(mism)) { chained = true; break; }
-        if (it == 0) note_mismatch();
+        ZN_HINT_FIXUP();
+        if (it == 0 && !(HM == 1 && hinted)) note_mismatch();
         need = mism;
         if (mism) s = e_prev;
       }
@@ -629,6 +693,7 @@ __device__ __forceinline__ bool zn_fused_wave(const ZnGeom& g, const uint8_t* __
       const int32_t e_last = __builtin_amdgcn_readlane(e, (int)(nact ? nact - 1u : 0u));
       if (!chained || J + N > seg) { ok = false; break; }
       carry = e_last; hi_dw = lo_dw;
+      hint_store(s);
       uint32_t lane_lo = 0, wdone = 0;
       do {
         const uint32_t base = J - JF;                            // < UNIT
@@ -712,11 +777,18 @@ __device__ __forceinline__ void zn_tail_merge_wg(ZnFusedLds& L, const ZnSeg& one
 // slot: stream w's symbols start at slot + w * ZN_TAIL_SEGPAD, the last, incomplete row of a stream is stored whole; tail_done[4 plane + stream] = 1 where it worked —
 // the merge workgroups / the generic merge kernel take a plane whose four flags are set from the scratch, anything else (raw / RLE / tiny planes, tableLog 12,
 // malformed blocks) is left to the serial generic code.
-__device__ void zn_decode_tail_wg(ZnFusedLds& L_, const ZnSeg& one, const ZnSeg* __restrict__ segs, uint32_t nseg, uint32_t bt,
+// (ZN_TU_LOCAL: this file is also the body of a second translation unit, zn_decode_hinted.hip — the hinted kernels compile beside the others instead of behind them —,
+//  and in the emulated build a device function is an ordinary one: that unit's copy is its own)
+#if defined(ZN_DECODE_HINTED_TU)
+#define ZN_TU_LOCAL static
+#else
+#define ZN_TU_LOCAL
+#endif
+ZN_TU_LOCAL __device__ void zn_decode_tail_wg(ZnFusedLds& L_, const ZnSeg& one, const ZnSeg* __restrict__ segs, uint32_t nseg, uint32_t bt,
                                   uint8_t* __restrict__ scratch, uint8_t* __restrict__ tail_done, uint32_t* __restrict__ status, uint32_t* tail0_out);
 #include "zn_decode_wide.hpp"
 
-__device__ void zn_decode_tail_wg(ZnFusedLds& L_, const ZnSeg& one, const ZnSeg* __restrict__ segs, uint32_t nseg, uint32_t bt,
+ZN_TU_LOCAL __device__ void zn_decode_tail_wg(ZnFusedLds& L_, const ZnSeg& one, const ZnSeg* __restrict__ segs, uint32_t nseg, uint32_t bt,
                                   uint8_t* __restrict__ scratch, uint8_t* __restrict__ tail_done, uint32_t* __restrict__ status, uint32_t* tail0_out) {
   ZnFusedLds& L = *ZN_LDS_PTR(ZnFusedLds, &L_);     // (this is a real call: keep the LDS accesses DS operations)
   const uint32_t b = bt >> 2, sq = zn_uniform(bt & 3u);     // tail plane of the launch / huff0 stream of its block
@@ -864,13 +936,30 @@ static_assert(sizeof(ZnFusedLds) * ZN_F_WAVES_PER_SIMD <= 160u * 1024u, "ZnFused
 // REST (launches without partial chunks and delta bases): a chunk this kernel does not take is decoded right here by the generic
 // path's own device functions (zn_decode_rest.hpp: one wave per plane, then the merge) instead of being left to two more launches that would
 // return at once in nearly every call; `descs_rest` = the launch's plane descriptors (the generic kernels' workspace).
-template <int P, bool X, bool REST = false>
-__global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void zn_k_decode_fused(ZnSeg one, const ZnSeg* __restrict__ segs, uint32_t nseg,
+// The HINTED kernels are this kernel's text under another name: zn_decode_hinted.hip compiles this file with ZN_DECODE_HINTED_TU set, and the
+// definition below is then zn_k_decode_hinted<P, X, REST, HM> — launched as <P, false, false, HM>: the plain instance, what it does not take is left to the generic
+// launches behind it — with two more arguments: the index of segment i is entry i of `hsegs`, a table parallel to `segs` (`one_h` beside `one`).  HM 1: its stream
+// decoders read the index (a segment without one, hints == null, decodes exactly as here); HM 2: they write it — launched without tail workgroups, and nothing but
+// hint bytes and the done flags is stored.  In this unit HM is the constant 0 and the kernel is, token for token, what it was before there were hints.
+#if defined(ZN_DECODE_HINTED_TU)
+#define ZN_K_DECODE_NAME zn_k_decode_hinted
+#define ZN_K_HM_TPARAM , int HM
+#define ZN_K_HM_PARAMS , ZnHintSeg one_h, const ZnHintSeg* __restrict__ hsegs
+#define ZN_K_HM_CONST
+#else
+#define ZN_K_DECODE_NAME zn_k_decode_fused
+#define ZN_K_HM_TPARAM
+#define ZN_K_HM_PARAMS
+#define ZN_K_HM_CONST constexpr int HM = 0; const ZnHintSeg one_h = {nullptr, 0}; const ZnHintSeg* const hsegs = nullptr; (void)one_h; (void)hsegs;
+#endif
+template <int P, bool X, bool REST = false ZN_K_HM_TPARAM>
+__global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void ZN_K_DECODE_NAME(ZnSeg one, const ZnSeg* __restrict__ segs, uint32_t nseg,
                                                                   uint8_t* __restrict__ done_all, uint8_t* __restrict__ pdone_all,
                                                                   uint32_t* __restrict__ status, uint32_t ntail,
                                                                   uint8_t* __restrict__ tail_scratch, uint8_t* __restrict__ tail_done, uint32_t only_pending,
                                                                   ZnPlaneDesc* __restrict__ descs_rest, uint32_t nchunk_wg, uint32_t merge_per,
-                                                                  uint32_t* __restrict__ tailsync) {
+                                                                  uint32_t* __restrict__ tailsync ZN_K_HM_PARAMS) {
+  ZN_K_HM_CONST
   constexpr int EPL = (P == 1) ? 16 : 8;
   constexpr uint32_t UNIT = 64u * EPL;
   __shared__ ZnFusedLds L;
@@ -902,7 +991,8 @@ __global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void zn_k_decode
   // (the segment comes back through private memory — a kernel argument or a table entry, chosen at run time — which makes
   //  every field per-lane data to the compiler: 64-bit pointers in vector registers, spilled and reloaded once per chunk,
   //  0.17 GB of scratch reads per GiB decoded.  They are uniform: scalar registers.)
-  const ZnSeg S_ = zn_find_seg<0>(one, segs, nseg, wg);
+  uint32_t seg_i = 0;                          // HM: the segment's index in the table — its hints are entry seg_i of the parallel table
+  const ZnSeg S_ = HM ? zn_find_seg<0>(one, segs, nseg, wg, &seg_i) : zn_find_seg<0>(one, segs, nseg, wg);
   ZnSeg S;
   S.g.n = zn_uniform64(S_.g.n); S.g.chunk = zn_uniform64(S_.g.chunk); S.g.K = zn_uniform64(S_.g.K); S.g.P = zn_uniform(S_.g.P); S.g.rot = zn_uniform(S_.g.rot);
   S.body = (const uint8_t*)zn_uniform64((uint64_t)S_.body); S.body_len = zn_uniform64(S_.body_len); S.dst = (uint8_t*)zn_uniform64((uint64_t)S_.dst);
@@ -997,6 +1087,7 @@ __global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void zn_k_decode
 
     uint32_t TL = 0;
     const uint8_t* stream = nullptr; uint32_t slen = 0;
+    uint32_t h_before = 0, h_mine = 0;       // HM: hint bytes of the streams ahead of this wave's / of its own
     bool bad = false;
     if (h >= 0) {
       // ---- decode tables ----
@@ -1014,6 +1105,10 @@ __global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void zn_k_decode
       if (l1 == 0 || l2 == 0 || l3 == 0 || l4 == 0) bad = true;
       const uint32_t so = 6u + (wave > 0 ? l1 : 0u) + (wave > 1 ? l2 : 0u) + (wave > 2 ? l3 : 0u);
       stream = js + so; slen = (wave == 0) ? l1 : (wave == 1) ? l2 : (wave == 2) ? l3 : l4;
+      if constexpr (HM != 0) {
+        const uint32_t b1 = zn_hint_stream_bytes(l1, seg, UNIT), b2 = zn_hint_stream_bytes(l2, seg, UNIT), b3 = zn_hint_stream_bytes(l3, seg, UNIT), b4 = zn_hint_stream_bytes(l4, seg, UNIT);
+        h_before = (wave > 0 ? b1 : 0u) + (wave > 1 ? b2 : 0u) + (wave > 2 ? b3 : 0u); h_mine = (wave == 0) ? b1 : (wave == 1) ? b2 : (wave == 2) ? b3 : b4;
+      }
       __syncthreads();                         // lut16 (aliasing ring[0]) is dead from here on
       ZN_PT(2);   // LUT fill
     }
@@ -1034,21 +1129,38 @@ __global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void zn_k_decode
     if (dense) Du = ZN_F_DCONST2;
     else if (ZN_F_DCAP && Du > ZN_F_DCAP && zn_uniform(L.st[j].dom) < ZN_F_DOM_MAX) Du = ZN_F_DCAP;
     Du = (uint32_t)__builtin_amdgcn_readfirstlane((int)Du);
+    // HM: this wave's part of the index — the (chunk, plane)'s region from the offset table at the head of the buffer, by the BODY's chunk
+    // number; inside it the four streams one behind the other, each zn_hint_stream_bytes long (a function of the jump table alone).  Every bound is checked
+    // against the buffer's length: a table that does not fit decodes without hints.
+    uint8_t* hq = nullptr; uint32_t hcap = 0;
+    if constexpr (HM != 0) {
+      ZnHintSeg hs_ = one_h; if (hsegs != nullptr) hs_ = hsegs[seg_i];
+      uint8_t* const hbuf = zn_uniform_ptr(hs_.hints); const uint64_t hlen = zn_uniform64(hs_.len);
+      const uint64_t kb_ = zn_uniform(S_.kb), ent = ((uint64_t)zn_uniform(S_.c_lo) + c) * (uint32_t)P + (uint32_t)(h < 0 ? 0 : h);
+      const uint64_t hdr = zn_hint_header_bytes(kb_ * (uint32_t)P);
+      if (h >= 0 && hbuf != nullptr && hlen >= hdr && ent < kb_ * (uint32_t)P) {
+        const uint32_t* offs = (const uint32_t*)hbuf;
+        const uint32_t o0 = zn_uniform(offs[ent]), o1 = zn_uniform(offs[ent + 1u]);
+        if (o0 >= hdr && o1 >= o0 && (uint64_t)o1 <= hlen && (uint64_t)h_before + h_mine <= (uint64_t)(o1 - o0)) { hq = hbuf + o0 + h_before; hcap = h_mine; }
+      }
+    }
     bool ok;
+#define ZN_HINT_ARGS , hq, hcap
 #define ZN_WAVE_ARGS g, body, body_end, outq, xq, pl, rawq, L.lut, ring, in, lane, seg, TL, Du, stream, slen, false ZN_PT_PASS
-#define ZN_WAVE_CASE(H_) ok = (Du == ZN_F_DCONST) ? zn_fused_wave<P, H_, ZN_F_DCONST, X>(ZN_WAVE_ARGS) \
-                            : (dense) ? zn_fused_wave<P, H_, ((X || P > 2 || !ZN_F_DCONST2) ? 0 : ZN_F_DCONST2), X>(ZN_WAVE_ARGS) \
-                            : zn_fused_wave<P, H_, 0, X>(ZN_WAVE_ARGS)
+#define ZN_WAVE_CASE(H_) ok = (Du == ZN_F_DCONST) ? zn_fused_wave<P, H_, ZN_F_DCONST, X, HM>(ZN_WAVE_ARGS ZN_HINT_ARGS) \
+                            : (dense) ? zn_fused_wave<P, H_, ((X || P > 2 || !ZN_F_DCONST2) ? 0 : ZN_F_DCONST2), X, HM>(ZN_WAVE_ARGS ZN_HINT_ARGS) \
+                            : zn_fused_wave<P, H_, 0, X, HM>(ZN_WAVE_ARGS ZN_HINT_ARGS)
     // (one instance per Huffman plane index that exists for this P — nothing is instantiated twice)
-    if (h < 0) ok = zn_fused_wave<P, -1, 0, X>(ZN_WAVE_ARGS);
+    if (h < 0) ok = zn_fused_wave<P, -1, 0, X, HM>(ZN_WAVE_ARGS ZN_HINT_ARGS);
     else if (P == 1 || h == 0) ZN_WAVE_CASE(0);
     else if (P == 2 || h == 1) ZN_WAVE_CASE((P >= 2 ? 1 : 0));
     else if (h == 2) ZN_WAVE_CASE((P >= 4 ? 2 : 0));
     else ZN_WAVE_CASE((P >= 4 ? 3 : 0));
 #undef ZN_WAVE_CASE
 #undef ZN_WAVE_ARGS
+#undef ZN_HINT_ARGS
     // ---- further Huffman planes (deltas, sparse tensors: every plane compresses): one more pass per plane
-    if (P >= 2 && __builtin_expect(more != 0u, 0)) {
+    if (HM != 2 && P >= 2 && __builtin_expect(more != 0u, 0)) {      // (further planes are decoded without hints; an index build has no rows to add them to)
       const int r2 = zn_fused_more_passes<P>(L, g, body, body_end, outq, j, more, seg ZN_PT_PASS);
       if (r2 < 0) { ZN_REST_CHUNK(c); ZN_SET_DONE(c, 0); continue; }   // a later plane this kernel does not take: the generic path redoes the chunk
       ok = ok && r2 > 0;
@@ -1059,6 +1171,88 @@ __global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void zn_k_decode
   }
   ZN_PT_FLUSH();
 }
+
+// The sizing pass of an index: one workgroup walks the body's type and size tables, 256 chunks at a time, and gives the FIRST Huffman-coded plane of every full
+// chunk the fused kernel would take a region of zn_hint_stream_bytes per huff0 stream (the jump table stands behind a tree description whose length is its first
+// byte's to say).  offs (may be null: size only) gets one 32-bit offset per (chunk, plane) — entry c P + p, from the start of the buffer, whose head the table
+// itself is — and the total as its last entry; *total the same in 64 bits (a total that does not fit 32 bits is refused by the host).
+#if defined(ZN_DECODE_HINTED_TU)
+__global__ __launch_bounds__(256) void zn_k_hint_size(ZnGeom g, const uint8_t* __restrict__ body, uint64_t body_len, uint32_t* __restrict__ offs, uint64_t* __restrict__ total) {
+  __shared__ uint32_t sh[256];
+  __shared__ uint64_t run;
+  const uint32_t tid = threadIdx.x, P = g.P;
+  const uint32_t unit = 64u * (P == 1u ? 16u : 8u);
+  const uint32_t plen = (uint32_t)(g.chunk / P), seg = plen / 4u;
+  const bool geom_ok = (g.chunk % (4ull * P * unit)) == 0;
+  const uint8_t* body_end = body + body_len;
+  if (tid == 0) run = zn_hint_header_bytes(g.K * P);
+  __syncthreads();
+  for (uint64_t base = 0; base < g.K; base += 256u) {
+    const uint64_t c = base + tid;
+    uint32_t sz = 0; int h = -1;
+    if (c < g.K && geom_ok && zn_chunk_len(g, c) == g.chunk) {
+      bool elig = true; ZnPcMeta mh; mh.off = 0; mh.csize = 0;
+      for (uint32_t p = 0; p < P; p++) {
+        const ZnPcMeta m = zn_pc_meta(g, (uint32_t)g.K, 0u, body, body_len, p, c);
+        uint32_t kind = 99u;
+        if (m.ok && m.type <= 1u) {
+          if (m.type == 0u) { if (m.csize >= plen) kind = ZN_KIND_RAW; }
+          else if (m.csize == plen) kind = ZN_KIND_RAW;
+          else if (m.csize == 1u) kind = ZN_KIND_RLE;
+          else if (m.csize > 1u && m.csize < plen) kind = ZN_KIND_HUF;
+        }
+        if (kind == 99u) elig = false;
+        if (kind == ZN_KIND_HUF && h < 0) { h = (int)p; mh = m; }
+      }
+      if (elig && h >= 0 && body + mh.off + mh.csize <= body_end) {
+        const uint8_t* src = body + mh.off;
+        const uint32_t h0 = src[0];
+        const uint32_t hs = 1u + (h0 >= 128u ? (h0 - 127u + 1u) / 2u : h0);
+        if (hs < mh.csize && mh.csize - hs >= 10u) {
+          const uint8_t* js = src + hs; const uint32_t rem = mh.csize - hs;
+          const uint32_t l1 = zn_ld16(js), l2 = zn_ld16(js + 2), l3 = zn_ld16(js + 4);
+          if (l1 && l2 && l3 && l1 + l2 + l3 + 6u < rem) {
+            const uint32_t l4 = rem - 6u - l1 - l2 - l3;
+            sz = zn_hint_stream_bytes(l1, seg, unit) + zn_hint_stream_bytes(l2, seg, unit) + zn_hint_stream_bytes(l3, seg, unit) + zn_hint_stream_bytes(l4, seg, unit);
+          }
+        }
+      }
+    }
+    // exclusive scan of the 256 sizes
+    sh[tid] = sz;
+    __syncthreads();
+    for (uint32_t d = 1; d < 256u; d <<= 1) {
+      const uint32_t v = (tid >= d) ? sh[tid - d] : 0u;
+      __syncthreads();
+      sh[tid] += v;
+      __syncthreads();
+    }
+    const uint64_t start = run + (sh[tid] - sz);
+    if (offs != nullptr && c < g.K) for (uint32_t p = 0; p < P; p++) offs[c * P + p] = (uint32_t)(start + (((int)p > h && h >= 0) ? sz : 0u));
+    __syncthreads();
+    if (tid == 255u) run += sh[255];
+    __syncthreads();
+  }
+  if (tid == 0) { if (offs != nullptr) offs[g.K * P] = (uint32_t)run; *total = run; }
+}
+
+void zn_launch_hint_size(const ZnGeom& g, const uint8_t* d_body, uint64_t body_len, uint32_t* d_offs, uint64_t* d_total, hipStream_t stream) {
+  hipLaunchKernelGGL(zn_k_hint_size, dim3(1), dim3(256), 0, stream, g, d_body, body_len, d_offs, d_total);
+  zn_note_kernel("zn_k_hint_size");
+}
+void zn_launch_decode_hinted(int P, int mode, const ZnSeg& one, const ZnSeg* d_segs, uint32_t nseg, const ZnHintSeg& one_h, const ZnHintSeg* d_hsegs, uint32_t total_wg,
+                             uint8_t* d_done, uint8_t* d_pdone, uint32_t* d_status, uint32_t ntail, uint8_t* d_tail_scratch, uint8_t* d_tail_done, hipStream_t stream) {
+  if (total_wg == 0) return;
+  const uint32_t ntail_wg = (mode == 2) ? 0u : 4u * ntail;      // (four tail workgroups per plane, at the front of the grid: zn_launch_decode_fused)
+#define ZN_GOH(P_, M_) hipLaunchKernelGGL((zn_k_decode_hinted<P_, false, false, M_>), dim3(total_wg + ntail_wg), dim3(ZN_F_THREADS), 0, stream, one, d_segs, nseg, d_done, d_pdone, d_status, ntail_wg, d_tail_scratch, d_tail_done, 0u, (ZnPlaneDesc*)nullptr, total_wg, 0u, (uint32_t*)nullptr, one_h, d_hsegs)
+  if (mode == 2) { if (P == 1) ZN_GOH(1, 2); else if (P == 2) ZN_GOH(2, 2); else ZN_GOH(4, 2); }
+  else { if (P == 1) ZN_GOH(1, 1); else if (P == 2) ZN_GOH(2, 1); else ZN_GOH(4, 1); }
+#undef ZN_GOH
+  zn_note_kernel(mode == 2 ? "zn_k_decode_hinted^build" : ntail_wg ? "zn_k_decode_hinted+tail" : "zn_k_decode_hinted");
+}
+#endif
+
+#if !defined(ZN_DECODE_HINTED_TU)
 
 #ifdef ZN_PHASE_TIMERS
 extern "C" int zn_debug_phase_read(unsigned long long* out, int reset) {
@@ -1159,3 +1353,4 @@ bool zn_launch_decode_fused(int P, const ZnSeg& one, const ZnSeg* d_segs, uint32
   zn_note_kernel(d_descs_rest ? (ntail && !wide ? "zn_k_decode_fused^rest+tail+merge" : "zn_k_decode_fused^rest") : wide ? "zn_k_decode_fused^pending" : delta ? (ntail ? "zn_k_decode_fused^delta+tail" : "zn_k_decode_fused^delta") : (ntail ? "zn_k_decode_fused+tail" : "zn_k_decode_fused"));
   return d_descs_rest != nullptr;
 }
+#endif   // !ZN_DECODE_HINTED_TU

@@ -61,6 +61,19 @@ bool zn_launch_decode_fused(int P, const ZnSeg& one, const ZnSeg* d_segs, uint32
 // path's own code (zn_decode_rest.hpp) — returns true then, and the caller leaves out zn_launch_decode_generic
 int zn_decode_use_wide(uint64_t total_full_chunks, bool delta, bool weights_like, uint64_t tail_wgs);     // weights_like: every tensor of the call is split with the sign rotate (bf16 / fp32)
 
+// ---- decode hints: a sidecar index of sub-block start positions for bodies that stay where they are : zn_decode_fused.hip ----
+// The index of one body is one device buffer: a table of P·kb + 1 32-bit offsets (entry c·P + p: where the hints of body chunk c, plane p start, counted from the
+// start of the buffer; the last entry: the buffer's length), padded to 64 bytes, then the hint bytes.  A launch's segments get theirs through a table parallel to
+// the segment table (or, for a single segment, a second kernel argument beside it); hints == null: that segment decodes without.
+struct ZnHintSeg { uint8_t* hints; uint64_t len; };
+static inline uint64_t zn_hint_header_bytes_host(uint64_t pk) { return ((pk + 1u) * 4u + 63u) & ~63ull; }
+// sizing pass: d_offs null = only the total (8 bytes at d_total)
+void zn_launch_hint_size(const ZnGeom& g, const uint8_t* d_body, uint64_t body_len, uint32_t* d_offs, uint64_t* d_total, hipStream_t stream);
+// mode 1: the hinted decode of a launch without delta bases and without the wide kernel in front — in place of zn_launch_decode_fused's plain instance: the caller
+// follows it with zn_launch_decode_generic.  mode 2: the index build (one whole body, no tail workgroups, no destination).
+void zn_launch_decode_hinted(int P, int mode, const ZnSeg& one, const ZnSeg* d_segs, uint32_t nseg, const ZnHintSeg& one_h, const ZnHintSeg* d_hsegs, uint32_t total_wg,
+                             uint8_t* d_done, uint8_t* d_pdone, uint32_t* d_status, uint32_t ntail, uint8_t* d_tail_scratch, uint8_t* d_tail_done, hipStream_t stream);
+
 // ---- encode ----
 struct ZnEncDesc {           // per (plane, chunk): what the emit kernel needs for a plane kept as huff0 / RLE
   uint32_t code[256];        // code value | code length << 16

@@ -14,6 +14,9 @@ import torch
 from . import _capi, codec
 from .zipnn import _ST_DTYPE_NAME, COMPRESSION_METHOD, ZipNN, dtype_from_user, index_rows
 
+# (see ResidentCheckpoint.INDEX_DTYPES)
+_INDEX_DTYPES = (torch.bfloat16, torch.float16, torch.float32) + tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e5m2") if hasattr(torch, n))
+
 ALIGN = 256          # decode destinations inside a shared buffer start at multiples of this (the fused kernel wants 16-byte aligned destinations)
 
 
@@ -52,10 +55,11 @@ class _device_of:
 
 class _Entry:
     """One tensor of the store: a frame body in device memory (`body`, with its codec parameters), or the tensor itself (`raw`)."""
-    __slots__ = ("name", "dtype", "shape", "nbytes", "body", "raw", "P", "bits", "byts", "chunk")
+    __slots__ = ("name", "dtype", "shape", "nbytes", "body", "raw", "P", "bits", "byts", "chunk", "hints")
 
     def __init__(self, name, dtype, shape, nbytes, body=None, raw=None, params=None):
         self.name, self.dtype, self.shape, self.nbytes, self.body, self.raw = name, dtype, tuple(int(d) for d in shape), int(nbytes), body, raw
+        self.hints = None                      # the body's decode hints (ResidentCheckpoint.build_index): a uint8 tensor beside the body, or None
         self.P, self.bits, self.byts, self.chunk = params if params is not None else (0, 0, 0, 0)
 
     @property
@@ -69,6 +73,11 @@ class _Entry:
     def window(self, lo, hi, dst_ptr):
         """-> the item tuple of ZnLib.decompress_window_batch_dev / plan_create for chunks [lo, hi) of this tensor."""
         return (self.body.data_ptr(), self.body.numel(), self.P, self.bits, self.byts, self.chunk, self.nbytes, lo, hi, dst_ptr)
+
+    def hinted(self, lo, hi, dst_ptr):
+        """-> the item of ZnLib.decompress_hinted_batch_dev / plan_create_hinted: the window plus the body's index (None, 0 without one)."""
+        h = self.hints
+        return (self.window(lo, hi, dst_ptr), h.data_ptr() if h is not None else None, h.numel() if h is not None else 0)
 
     def view(self, flat):
         """flat uint8 bytes of the whole tensor -> the tensor."""
@@ -93,6 +102,8 @@ class ResidentCheckpoint:
         self._entries = {e.name: e for e in entries}
         self._held = int(held_bytes)
         self._keep = tuple(keep)              # the allocations the entries are views of
+        self._index = None                     # the allocation the entries' hints are views of (build_index)
+        self._index_bytes = 0
 
     # ---- constructors -------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -107,8 +118,9 @@ class ResidentCheckpoint:
         return dev
 
     @classmethod
-    def from_file(cls, path, device="cuda:0"):
-        """A `.znn.safetensors` file (this library's or the reference's): its data section goes to `device` once, in one transfer, and stays."""
+    def from_file(cls, path, device="cuda:0", index=False):
+        """A `.znn.safetensors` file (this library's or the reference's): its data section goes to `device` once, in one transfer, and stays.
+        index=True: build_index() on the new store."""
         from . import safetensors_io
         dev = cls._work_device(device)
         up = safetensors_io._upload_file(path, dev)
@@ -134,13 +146,16 @@ class ResidentCheckpoint:
             else:
                 raw = torch.empty(shape, dtype=dt, device=dev)
             entries.append(_Entry(name, dt, shape, hi - lo, raw=raw))
-        return cls(dev, entries, blob.numel() + extra, keep=(blob,))
+        store = cls(dev, entries, blob.numel() + extra, keep=(blob,))
+        if index:
+            store.build_index()
+        return store
 
     @classmethod
-    def from_state_dict(cls, sd, device="cuda:0", threshold=0.95, method=None):
+    def from_state_dict(cls, sd, device="cuda:0", threshold=0.95, method=None, index=False):
         """Compress the tensors of a state dict on `device` (one batched call) and keep the bodies, trimmed to their lengths and packed at
         256-byte boundaries of one allocation.  A tensor whose body would not be smaller than the tensor itself — and every tensor the codec
-        does not take: integers, float64, empty ones — is kept as it is."""
+        does not take: integers, float64, empty ones — is kept as it is.  index=True: build_index() on the new store."""
         dev = cls._work_device(device)
         lib = _capi.lib()
         todo, entries = [], {}
@@ -172,7 +187,68 @@ class ResidentCheckpoint:
             held += o
             del bodies                         # (the compress arena — as large as the tensors themselves — goes back to the allocator)
         held += sum(e.nbytes for e in entries.values() if not e.compressed)
-        return cls(dev, [entries[name] for name in sd.keys()], held, keep=keep)
+        store = cls(dev, [entries[name] for name in sd.keys()], held, keep=keep)
+        if index:
+            store.build_index()
+        return store
+
+    # ---- the sync index ---------------------------------------------------------------------------------------------------------
+    #: dtypes build_index() indexes by default; build_index(all_dtypes=True) indexes every compressed tensor.  The rule: a dtype whose hinted decode does
+    #: not measure faster than the unhinted one by more than the run's own A/A spread (scripts/bench_resident.py --index) is taken out of this set.
+    #: No dtype has been timed on a device yet, so none has been taken out.
+    INDEX_DTYPES = frozenset(_INDEX_DTYPES)
+
+    def build_index(self, names=None, all_dtypes=False):
+        """Decode hints for the resident bodies (include/zipnn_hip.h): one pass over each body records where the decoder's sub-blocks
+        start — about a byte per 16-24 bytes of Huffman-coded plane — so that every later decode of it (get_tensor, get_tensors, get_slice, plan,
+        hook: no further arguments) starts them there instead of finding them by speculation.  The hints sit beside the bodies in device memory,
+        never in them, and are advice: the decoded bytes are the same with and without.  names: the tensors to index (default: every compressed
+        one); a dtype that measured no gain is left out unless all_dtypes is set.  Tensors already indexed keep their index; plans and hooks made
+        before this call go on decoding without."""
+        lib = _capi.lib()
+        todo = []
+        for name in (self.keys() if names is None else names):
+            e = self._entries[name]
+            if e.compressed and e.nbytes and e.hints is None and (all_dtypes or e.dtype in self.INDEX_DTYPES):
+                todo.append(e)
+        if not todo:
+            return 0
+        with _device_of(self.device):
+            stream = _stream_of(self.device)
+            sizes = [lib.hint_size_dev(e.window(0, e.chunks, None), stream) for e in todo]
+            offs, o = [], 0
+            for n in sizes:
+                offs.append(o)
+                o += _round_up(n)
+            buf = torch.empty(max(o, 1), dtype=torch.uint8, device=self.device)
+            for e, n, off in zip(todo, sizes, offs):
+                lib.hint_build_dev(e.window(0, e.chunks, None), buf.data_ptr() + off, n, stream)
+                e.hints = buf[off:off + n]
+        self._index = (self._index or ()) + (buf,)
+        self._index_bytes += o
+        self._held += o
+        return o
+
+    def drop_index(self):
+        """Free the hints.  Plans and hooks made while the index existed must be closed / removed first: they refer to it by address."""
+        for e in self._entries.values():
+            e.hints = None
+        self._held -= self._index_bytes
+        self._index, self._index_bytes = None, 0
+
+    @property
+    def index_bytes(self):
+        """Bytes of device memory the index holds (part of resident_bytes)."""
+        return self._index_bytes
+
+    def _decode(self, work, check):
+        """work: [(entry, chunk_lo, chunk_hi, dst_ptr)] -> one batched decode on the current stream, hinted when an entry has an index."""
+        lib = _capi.lib()
+        with _device_of(self.device):
+            if any(e.hints is not None for e, _, _, _ in work):
+                lib.decompress_hinted_batch_dev([e.hinted(lo, hi, dp) for e, lo, hi, dp in work], _stream_of(self.device), check)
+            else:
+                lib.decompress_window_batch_dev([e.window(lo, hi, dp) for e, lo, hi, dp in work], _stream_of(self.device), check)
 
     # ---- introspection --------------------------------------------------------------------------------------------------------
     def keys(self):
@@ -187,7 +263,7 @@ class ResidentCheckpoint:
     def info(self, name):
         e = self._entries[name]
         return {"shape": list(e.shape), "dtype": e.dtype, "nbytes": e.nbytes, "compressed": e.compressed,
-                "resident_bytes": e.body.numel() if e.compressed else e.nbytes}
+                "resident_bytes": e.body.numel() if e.compressed else e.nbytes, "index_bytes": e.hints.numel() if e.hints is not None else 0}
 
     @property
     def nbytes(self):
@@ -242,8 +318,7 @@ class ResidentCheckpoint:
         if out is None:
             out = torch.empty(e.shape, dtype=e.dtype, device=self.device)
         if e.nbytes:
-            with _device_of(self.device):
-                _capi.lib().decompress_window_batch_dev([e.window(0, e.chunks, out.data_ptr())], _stream_of(self.device), check)
+            self._decode([(e, 0, e.chunks, out.data_ptr())], check)
         return out
 
     def get_tensors(self, names, into=None, check=True):
@@ -252,8 +327,7 @@ class ResidentCheckpoint:
         they are (views of the store: do not write to them)."""
         views, work = self._destinations(names, into)
         if work:
-            with _device_of(self.device):
-                _capi.lib().decompress_window_batch_dev([e.window(0, e.chunks, flat.data_ptr()) for e, flat in work], _stream_of(self.device), check)
+            self._decode([(e, 0, e.chunks, flat.data_ptr()) for e, flat in work], check)
         return views
 
     def get_slice(self, name):
@@ -308,8 +382,7 @@ class ResidentSlice:
             self.last_chunk_range = (c_lo, c_hi)
             base = c_lo * chunk
             buf = torch.empty(min(c_hi * chunk, n) - base, dtype=torch.uint8, device=dev)      # (torch's allocator orders the block's reuse on the current stream: the decode runs there)
-            with _device_of(dev):
-                _capi.lib().decompress_window_batch_dev([e.window(c_lo, c_hi, buf.data_ptr())], _stream_of(dev), False)
+            self._s._decode([(e, c_lo, c_hi, buf.data_ptr())], False)
             t = buf[byte_lo - base: byte_hi - base].view(e.dtype).reshape(() if scalar else (b - a,) + shape[1:])
         return t[sel] if sel else t
 
@@ -327,7 +400,11 @@ class ResidentPlan:
         self._stream = None
         self._h = None
         with _device_of(store.device):
-            self._h = self._lib.plan_create([e.window(0, e.chunks, flat.data_ptr()) for e, flat in work])
+            if any(e.hints is not None for e, _ in work):
+                self._keep += [e.hints for e, _ in work if e.hints is not None]
+                self._h = self._lib.plan_create_hinted([e.hinted(0, e.chunks, flat.data_ptr()) for e, flat in work])
+            else:
+                self._h = self._lib.plan_create([e.window(0, e.chunks, flat.data_ptr()) for e, flat in work])
 
     def run(self, stream=None):
         if self._h is None:
