@@ -422,3 +422,187 @@ def test_two_tensor_store_decodes_hinted_on_a_fresh_workspace(use_simt):
         assert c[0] > 0 and c[1] == 0
     finally:
         use_simt.set_decode_wide(1)
+
+
+# ---- index tables past one sizing block, hostile distributions, mixed chunk groups (tests/test_gpu_resident_index.py runs the same shapes on hardware) ----
+
+# (kind, chunk, chunks, extra bytes): zn_k_hint_size sizes 256 chunks per iteration and carries the running offset to the next — below, at, one past 256, a
+# partial last chunk behind 300, past 512; four planes and one plane past 256
+TABLES = [("bf16", 4096, 255, 0), ("bf16", 4096, 256, 0), ("bf16", 4096, 257, 0), ("bf16", 4096, 300, 100), ("bf16", 4096, 520, 0),
+          ("fp32", 8192, 260, 0), ("fp8", 4096, 258, 0)]
+TABLE_WINDOWS = [(250, 290), (255, 258), (511, 514)]
+
+
+def _table_id(c):
+    return f"{c[0]}-{c[2]}x{c[1]}" + (f"+{c[3]}B" if c[3] else "")
+
+
+def _table_windows(K):
+    """The windows of the table tests that lie inside K chunks (clipped at K), and the last chunk alone."""
+    return [(lo, min(hi, K)) for lo, hi in TABLE_WINDOWS if lo < K] + [(K - 1, K)]
+
+
+def _shifted(body0, shift):
+    """A copy of the body `shift` bytes into a 4-byte aligned buffer."""
+    big = torch.zeros(body0.numel() + 8, dtype=torch.uint8)
+    assert big.data_ptr() % 4 == 0
+    big[shift:shift + body0.numel()] = body0
+    return big[shift:shift + body0.numel()]
+
+
+def _check_index_bytes(h, n, spec, body):
+    """What holds for every index the build writes: the table is the layout rule's and non-decreasing; a hint is at most 10, lane 0's is 0."""
+    import hint_layout as HL
+    P, _, _, ch, nb = spec
+    want, hdr = HL.expected_table(body.numpy().tobytes(), P, ch, nb)
+    assert hdr == _header_bytes(spec) and int(want[-1]) == n
+    got = h[:4 * len(want)].numpy().view("<u4")
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, f"offset table differs from the layout rule first at entry {bad[0]} (chunk {bad[0] // P}): {got[bad[0]]} != {want[bad[0]]}"
+    assert bool((np.diff(got.astype(np.int64)) >= 0).all())
+    hints = h[hdr:n].numpy()
+    assert hints.size % 64 == 0
+    assert int(hints.max(initial=0)) <= 10
+    assert bool((hints[0::64] == 0).all())
+    return want
+
+
+@pytest.mark.parametrize("case", TABLES, ids=_table_id)
+def test_index_table_equals_the_layout_rule_across_sizing_blocks(fused, case):
+    """Hundreds of chunks: the sizing kernel's running offset crosses its 256-chunk blocks (K below, at, past a multiple of 256; windows whose first chunk
+    lies past chunk 256 and 512).  The table equals tests/hint_layout.py's — the layout of DESIGN §3.6 restated without the kernels — and the decodes it
+    serves start every tile from a hint and need no fix-up."""
+    lib = fused
+    kind, chunk, chunks, extra = case
+    d, body, spec = _case(kind, chunks, 31, extra, chunk=chunk)
+    K = -(-len(d) // chunk)
+    n = lib.hint_size_dev(_item(body, spec))
+    h = torch.full((n + 256,), 0xFF, dtype=torch.uint8)      # (0xFF is no hint: what the build's tiles do not write must have been zeroed)
+    _hint_counters()
+    lib.hint_build_dev(_item(body, spec), h.data_ptr(), h.numel())
+    assert "zn_k_hint_size" in lib.last_kernels() and "zn_k_decode_hinted^build" in lib.last_kernels()
+    written = _hint_counters()[3]
+    assert 0 < written <= n - _header_bytes(spec)
+    _check_index_bytes(h, n, spec, body)
+    assert bool((h[n:] == 0xFF).all()), "the build wrote behind the index"
+    h = h[:n]
+    _hint_counters(); _tile_counters()
+    assert _decode(lib, [(body, spec, 0, K, h, None)])[0] == d
+    assert "zn_k_decode_hinted" in lib.last_kernels()
+    hc = _hint_counters()
+    assert hc[0] > 0 and hc[1] == 0 and hc[2] == 0, hc
+    for lo, hi in _table_windows(K):
+        _hint_counters()
+        got = _decode(lib, [(body, spec, lo, hi, h, None)])[0]
+        assert got == d[lo * chunk: min(hi * chunk, len(d))], (lo, hi)
+        hc = _hint_counters()
+        assert hc[1] == 0 and hc[2] == 0, (lo, hi, hc)
+        if (lo + 1) * chunk <= len(d):
+            assert hc[0] > 0, (lo, hi, hc)
+
+
+def test_index_of_a_body_three_bytes_into_its_buffer_serves_a_window_past_chunk_512(fused):
+    """Tile boundaries move with the body's address modulo 4, and the hints with them: the table is the same, the bytes are not, and a window whose first
+    chunk lies in the sizing kernel's third block decodes from them without a fix-up."""
+    lib = fused
+    kind, chunk, chunks, extra = TABLES[4]
+    assert chunks == 520
+    d, body, spec = _case(kind, chunks, 31, extra, chunk=chunk)
+    sb = _shifted(body, 3)
+    hs, ns = _build(lib, sb, spec)
+    want = _check_index_bytes(hs, ns, spec, sb)
+    P = spec[0]
+    for lo, hi, bd in ((511, 514, sb), (511, 514, body)):
+        _hint_counters()
+        assert _decode(lib, [(bd, spec, lo, hi, hs, None)])[0] == d[lo * chunk: hi * chunk]
+        hc = _hint_counters()
+        assert hc[0] > 0 and hc[2] == 0, hc
+        assert (hc[1] == 0) == (bd is sb), hc      # (at another address the same hints are bad guesses: fix-ups, the same bytes)
+    assert int(want[514 * P]) > int(want[511 * P])
+
+
+# (kind, planes, bits_mode, bytes_mode, chunk, chunks, every plane Huffman-coded): other instances of zn_fused_wave than weights take — 1-bit codes (the smallest
+# sub-blocks, where zn_hint_stream_bytes is tightest), tiles written in several lane groups, 11-bit codes (g up to 10), further planes decoded unhinted behind a
+# hinted first one; rand and const have no Huffman plane: their index is the header alone
+HOSTILE = [("skew", 1, 1, 10, 128 * 1024, 2, False), ("skew", 2, 0, 10, C2, 2, True), ("skew", 4, 1, 220, C2, 2, True), ("burst", 1, 1, 10, 128 * 1024, 2, False),
+           ("burst16", 2, 0, 10, 256 * 1024, 2, False), ("burst16", 2, 0, 10, C2, 3, False), ("u11", 2, 1, 10, C2, 4, False),
+           ("rand", 2, 1, 10, C2, 2, False), ("const", 2, 1, 10, C2, 2, False)]
+
+
+def _hostile(case, seed=13):
+    kind, P, rot, bm, chunk, chunks, _ = case
+    key = ("hostile", kind, P, rot, chunk, chunks, seed)
+    if key not in _CACHE:
+        d = _gen2(kind, chunks * chunk, seed)
+        _CACHE[key] = (d, _u8(O.compress_frame(b"", d, P, rot, bm, chunk)), (P, rot, bm, chunk, len(d)))
+    return _CACHE[key]
+
+
+@pytest.mark.parametrize("case", HOSTILE, ids=lambda c: f"{c[0]}-P{c[1]}-r{c[2]}-c{c[4] // 1024}k")
+def test_hinted_decode_of_hostile_distributions(fused, case):
+    lib = fused
+    kind, P, rot, bm, chunk, chunks, all_huf = case
+    d, body, spec = _hostile(case)
+    h, n = _build(lib, body, spec)
+    _check_index_bytes(h, n, spec, body)
+    _hint_counters(); _tile_counters()
+    assert _decode(lib, [(body, spec, 0, chunks, h, None)])[0] == d
+    tiles, hc = _tile_counters(), _hint_counters()
+    print(f"{kind} P{P}: tiles {tiles[0]}, looping {tiles[1]}, in lane groups {tiles[3]}, hinted {hc[0]}, with fix-up {hc[1]}, unhinted {hc[2]}, index {n} B")
+    assert hc[1] == 0, hc
+    if kind in ("rand", "const"):
+        assert n == _header_bytes(spec) == 64 and hc[0] == 0
+    else:
+        assert "zn_k_decode_hinted" in lib.last_kernels()
+        assert hc[0] > 0
+        if all_huf:
+            assert hc[0] < tiles[0], (hc, tiles)      # the further planes' tiles take the run-in
+        else:
+            assert hc[0] == tiles[0], (hc, tiles)
+    assert _decode(lib, [(body, spec, 0, chunks, None, None)])[0] == d      # … and without the index (a store after drop_index)
+    assert "hinted" not in lib.last_kernels()
+
+
+def _mixed_kinds_body():
+    """The 11-chunk body of test_kernels_simt.test_fused_decode_chunk_groups (bf16, raw, RLE, 11-bit codes, two Huffman planes per chunk, at 16 KiB chunks)
+    and its 1000-byte partial tail -> (source, body tensor, spec, kinds per chunk)."""
+    if "mixed" not in _CACHE:
+        ch = 16384
+        r = np.random.default_rng(5)
+        parts, kinds = [], []
+        for k in range(11):
+            kind = ["bf16", "rand", "const", "u11", "skewpair", "bf16"][k % 6]
+            kinds.append(kind)
+            if kind == "skewpair":
+                parts.append(r.choice(np.array([1, 2, 3, 4], dtype=np.uint8), ch, p=[0.7, 0.1, 0.1, 0.1]).tobytes())
+            else:
+                parts.append(_gen2(kind, ch, 20 + k))
+        d = b"".join(parts) + _gen2("bf16", 1000, 3)
+        _CACHE["mixed"] = (d, _u8(O.compress_frame(b"", d, 2, 0, 10, ch)), (2, 0, 10, ch, len(d)), kinds)
+    return _CACHE["mixed"]
+
+
+def _mixed_table_check(h, n, spec, body, kinds):
+    """The table is the layout rule's; raw and RLE chunks and the partial tail have no region, every other chunk has one."""
+    want = _check_index_bytes(h, n, spec, body)
+    P = spec[0]
+    for c, kind in enumerate(kinds + ["tail"]):
+        size = int(want[(c + 1) * P]) - int(want[c * P])
+        assert (size == 0) == (kind in ("rand", "const", "tail")), (c, kind, size)
+
+
+@pytest.mark.parametrize("group", [1, 2, 3, 4])
+def test_hinted_chunk_groups_of_mixed_kinds(fused, decode_group, group):
+    """A workgroup's group of chunks mixes Huffman, raw, RLE and two-Huffman-plane chunks, and the call has a partial tail: built at the automatic
+    grouping, decoded at every group size."""
+    lib = fused
+    d, body, spec, kinds = _mixed_kinds_body()
+    decode_group(lib, 0)
+    h, n = _build(lib, body, spec)
+    _mixed_table_check(h, n, spec, body, kinds)
+    decode_group(lib, group)
+    _hint_counters()
+    assert _decode(lib, [(body, spec, 0, 12, h, None)])[0] == d
+    assert "zn_k_decode_hinted+tail" in lib.last_kernels(), lib.last_kernels()
+    hc = _hint_counters()
+    assert hc[0] > 0 and hc[1] == 0, hc
