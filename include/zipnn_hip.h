@@ -189,7 +189,14 @@ int zn_plan_create_hinted(const zn_hinted_item* items, size_t count, zn_plan** p
 /* Delta ("byte"/"file" delta_compressed_type of the reference, zipnn/zipnn.py:625-640 and :983-1004: the bytes
  * are XORed with a second buffer of the same length before compression and after decompression).  The XOR is
  * fused into the kernels that read the tensor / write the output — no extra pass over HBM.  d_delta = NULL gives
- * zn_compress_dev / zn_decompress_dev.  Batched: set d_delta in the items above. */
+ * zn_compress_dev / zn_decompress_dev.  Batched: set d_delta in the items above.
+ * IN PLACE: in zn_decompress_delta_dev, zn_decompress_batch_dev, zn_decompress_window_batch_dev, zn_decompress_hinted_batch_dev and plans an item's
+ * destination may BE its base — a whole tensor: d_dst == d_delta; a window: d_dst == (char*)d_delta + chunk_lo * chunk.  The destination then ends as
+ * decoded ^ (what it held), the bytes a decode into a separate buffer gives, in every form of the decoder: any address alignment, partial last chunks, every
+ * chunk the fused kernel hands down.  XOR is its own inverse: the same call (a plan run a second time) over the result gives the base back — a tensor that
+ * holds a base model's weights becomes the fine-tune's and the base's again without a second copy.  Exactly that aliasing and no other: a base that overlaps
+ * its destination in any other way is undefined, as are two items of a call that write the same bytes.  A call that fails (ZN_E_CORRUPT, ZN_E_TYPE) leaves
+ * an in-place destination undefined like any other — the base with it. */
 int zn_compress_delta_dev(const void* d_src, const void* d_delta, size_t n, int num_buf, int bits_mode,
                           int bytes_mode, size_t chunk, float threshold, void* d_body, size_t body_cap,
                           size_t* body_len, void* stream);
@@ -317,6 +324,10 @@ int zn_release_workspace(void);
  * vouch for it") rather than a guess.  A thread whose most recent check = 0 call was not on this device (it made none, or its last one
  * went to another device) gets the device's most recent decode: ask on the device you launched on, before you launch on another. */
 int zn_decode_status(void* stream);
+/* on != 0: from now on the calling thread's check = 0 decode calls (batches, windows, plan runs) on a device ADD their verdict to the status of its previous
+ * check = 0 call there instead of starting a new one, so that one zn_decode_status speaks for a sequence of calls — a base decoded into a buffer and a delta
+ * decoded in place over it.  The calls of a sequence run on one stream.  on == 0: back to one status per call.  Returns 0. */
+int zn_decode_status_chain(int on);
 
 /* Names of the kernels the last *_dev call launched, ';'-separated (for profiles). */
 const char* zn_last_kernels(void);

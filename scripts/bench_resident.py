@@ -14,6 +14,12 @@ Each leg runs in a child process under a time limit of its own; a leg that fails
   i  per dtype (bf16, fp32, fp16, fp8 e4m3; about 1 GiB each, N(0, 0.02)): plan.run unhinted / hinted / unhinted / hinted on the same store, the build time
      per GiB and index_bytes / nbytes
   j  the four Llama-3-8B blocks of leg b, per block unhinted / hinted / unhinted / hinted, and leg e's hooked forward with and without the index
+--delta: variant stores instead (ResidentCheckpoint.from_state_dict(..., base=...)), into profiles/resident_delta.{json,txt}: the blocks of leg b as
+the base and two fine-tunes of them — (a) the base with 2 % of the elements replaced (the input of DESIGN §3.4), (b) every element moved by a small relative
+step, so that low mantissa bits change everywhere:
+  k  per fine-tune: variant resident bytes against a plain store of the same tensors; plan.run of one block from the plain store, from a variant over plain
+     base tensors and from a variant over a resident base, interleaved (A B C A B C: the plain store's two runs are the A/A spread); apply_ + revert_ of
+     one block; store build times
 """
 import argparse
 import json
@@ -27,6 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 LEG_SECONDS = {"a": 240, "b": 240, "c": 300, "d": 240, "e": 300}
 INDEX_LEG_SECONDS = {"i": 420, "j": 300}
+DELTA_LEG_SECONDS = {"k": 420}
 CH = 256 * 1024
 
 
@@ -288,6 +295,107 @@ def leg_j(args):
     return out
 
 
+def _fine_tune(sd, kind, seed):
+    """(a) "sparse": 2 % of the elements replaced by fresh N(0, 0.02) values; (b) "drift": every element times 1 + 2^-7 N(0, 1), rounded back to bf16."""
+    import torch
+    g = torch.Generator(device="cuda"); g.manual_seed(seed)
+    out = {}
+    for k, v in sd.items():
+        if kind == "sparse":
+            t = v.clone()
+            hit = torch.rand(v.shape, generator=g, device="cuda") < 0.02
+            t[hit] = (torch.randn(int(hit.sum()), generator=g, device="cuda") * 0.02).to(v.dtype)
+        else:
+            t = (v.float() * (1.0 + torch.randn(v.shape, generator=g, device="cuda") / 128.0)).to(v.dtype)
+        out[k] = t
+    return out
+
+
+def leg_k(args):
+    import torch
+    from zipnn_amd import ResidentCheckpoint
+    sd, per = _blocks(args.layers)
+    names = per[0]
+    res = {"layers": args.layers, "block_bytes": sum(sd[k].numel() * 2 for k in names), "fine_tunes": []}
+
+    def timed(fn):
+        torch.cuda.synchronize(); t0 = time.perf_counter(); r = fn(); torch.cuda.synchronize()
+        return r, time.perf_counter() - t0
+    base_store, t_base = timed(lambda: ResidentCheckpoint.from_state_dict(sd, "cuda:0", index=True))
+    res["base"] = {"nbytes": base_store.nbytes, "resident_bytes": base_store.resident_bytes, "index_bytes": base_store.index_bytes, "build_s": t_base}
+    for kind in ("sparse", "drift"):
+        ft = _fine_tune(sd, kind, 21)
+        plain, t_plain = timed(lambda: ResidentCheckpoint.from_state_dict(ft, "cuda:0"))
+        over_dict, t_dict = timed(lambda: ResidentCheckpoint.from_state_dict(ft, "cuda:0", base=sd))
+        over_store, t_store = timed(lambda: ResidentCheckpoint.from_state_dict(ft, "cuda:0", base=base_store))
+        r = {"kind": kind, "nbytes": plain.nbytes, "plain_resident_bytes": plain.resident_bytes, "variant_resident_bytes": over_dict.resident_bytes,
+             "variant_over_store_resident_bytes": over_store.resident_bytes, "delta_entries": sum(1 for k in ft if over_dict.info(k)["delta"] is True),
+             "tensors": len(ft), "build_s": {"plain": t_plain, "over_tensors": t_dict, "over_store": t_store}}
+        scratch = torch.empty(plain.scratch_bytes(names), dtype=torch.uint8, device="cuda")
+        runs = {"plain": [], "over_tensors": [], "over_store": []}
+        kernels = {}
+        for _ in range(2):                                    # A B C A B C
+            for leg, st in (("plain", plain), ("over_tensors", over_dict), ("over_store", over_store)):
+                plan = st.plan(names, into=scratch)
+                t = _events_ms(plan.run, args.reps)
+                plan.status()
+                for k in names:
+                    assert _same(plan.tensors[k], ft[k]), (kind, leg, k)
+                runs[leg].append(t["median_ms"])
+                kernels[leg] = _capi_kernels()
+                plan.close()
+        r["plan_run_ms"] = runs
+        r["kernels"] = kernels
+        r["aa_spread"] = abs(runs["plain"][0] - runs["plain"][1]) / min(runs["plain"])
+        # apply_ + revert_ of one block on tensors that hold the base (each leaves the tensors as it found them after the pair)
+        live = {k: sd[k].clone() for k in names}
+        t_ar = _events_ms(lambda: (over_store.apply_(live, check=False), over_store.revert_(live, check=False)), args.reps)
+        over_store.status()
+        for k in names:
+            assert _same(live[k], sd[k]), (kind, "revert", k)
+        over_store.apply_(live)
+        for k in names:
+            assert _same(live[k], ft[k]), (kind, "apply", k)
+        r["apply_revert_ms"] = t_ar["median_ms"]
+        r["apply_kernels"] = _capi_kernels()
+        res["fine_tunes"].append(r)
+        del plain, over_dict, over_store, ft, live, scratch
+        torch.cuda.empty_cache()
+    return res
+
+
+def main_delta(args):
+    results = {}
+    for leg, limit in DELTA_LEG_SECONDS.items():
+        p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--layers", str(args.layers), "--reps", str(args.reps)],
+                           capture_output=True, text=True)
+        line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+        if p.returncode != 0 or not line:
+            print(f"leg {leg} failed (exit {p.returncode}); nothing further is started\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}")
+            return 1
+        results[leg] = json.loads(line[0][7:])
+        print(f"leg {leg}: ok", flush=True)
+    out = args.out if args.out != os.path.join(ROOT, "profiles", "resident_decode") else os.path.join(ROOT, "profiles", "resident_delta")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    json.dump(results, open(out + ".json", "w"), indent=1)
+    k = results["k"]
+    lines = [f"variant store probe (ResidentCheckpoint.from_state_dict(..., base=...)): {k['layers']} Llama-3-8B blocks, bf16; device events, median ms; every result checked against its source",
+             f"base store: {k['base']['resident_bytes']} of {k['base']['nbytes']} bytes resident (index {k['base']['index_bytes']} B), built in {k['base']['build_s']:.2f} s"]
+    for r in k["fine_tunes"]:
+        lines.append(f"({r['kind']}) resident: variant {r['variant_resident_bytes']} B = {r['variant_resident_bytes'] / r['nbytes']:.4f} of the tensors, plain store {r['plain_resident_bytes']} B = "
+                     f"{r['plain_resident_bytes'] / r['nbytes']:.4f}; {r['delta_entries']} of {r['tensors']} tensors delta-coded")
+        q = r["plan_run_ms"]
+        lines.append(f"    plan.run of one block ({k['block_bytes']} B): plain store {q['plain'][0]:.4f} / {q['plain'][1]:.4f} (A/A spread {100 * r['aa_spread']:.1f} %), variant over plain tensors "
+                     f"{q['over_tensors'][0]:.4f} / {q['over_tensors'][1]:.4f}, variant over a resident base {q['over_store'][0]:.4f} / {q['over_store'][1]:.4f}")
+        lines.append(f"    apply_ + revert_ of one block: {r['apply_revert_ms']:.4f} ms   [{r['apply_kernels']}]")
+        b = r["build_s"]
+        lines.append(f"    store build: plain {b['plain']:.2f} s, variant over plain tensors {b['over_tensors']:.2f} s, over a resident base {b['over_store']:.2f} s")
+        lines.append(f"    kernels: over tensors [{r['kernels']['over_tensors']}]  over store [{r['kernels']['over_store']}]")
+    open(out + ".txt", "w").write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+    return 0
+
+
 def main_index(args):
     results = {}
     for leg, limit in INDEX_LEG_SECONDS.items():
@@ -325,6 +433,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--leg", default=None)
     ap.add_argument("--index", action="store_true", help="the sync index legs (i, j) instead of a-e")
+    ap.add_argument("--delta", action="store_true", help="the variant store leg (k) instead of a-e")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resident_decode"))
     args = ap.parse_args()
     if args.leg:                                          # a child: one leg, its result as one JSON line
@@ -332,6 +441,8 @@ def main():
         return 0
     if args.index:
         return main_index(args)
+    if args.delta:
+        return main_delta(args)
     results = {}
     for leg, limit in LEG_SECONDS.items():
         p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--layers", str(args.layers), "--reps", str(args.reps)],

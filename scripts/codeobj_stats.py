@@ -21,6 +21,8 @@ HOT = [("zn_k_decode_fusedILi1ELb0ELb0E", "decode_fused<1> plain"), ("zn_k_decod
        ("zn_k_decode_fusedILi4ELb0ELb0E", "decode_fused<4> plain"),
        ("zn_k_decode_fusedILi1ELb0ELb1E", "decode_fused<1> rest"), ("zn_k_decode_fusedILi2ELb0ELb1E", "decode_fused<2> rest"), ("zn_k_decode_fusedILi4ELb0ELb1E", "decode_fused<4> rest"),
        ("zn_k_decode_fusedILi2ELb1ELb0E", "decode_fused<2> delta"),
+       ("zn_k_decode_fusedILi4ELb1ELb0E", "decode_fused<4> delta"),
+       ("zn_k_decode_fusedILi2ELb1ELb1E", "decode_fused<2> delta, in place"), ("zn_k_decode_fusedILi4ELb1ELb1E", "decode_fused<4> delta, in place"),
        ("zn_k_decode_hintedILi1ELb0ELb0ELi1E", "decode_hinted<1> read"), ("zn_k_decode_hintedILi2ELb0ELb0ELi1E", "decode_hinted<2> read"),
        ("zn_k_decode_hintedILi4ELb0ELb0ELi1E", "decode_hinted<4> read"), ("zn_k_decode_hintedILi2ELb0ELb0ELi2E", "decode_hinted<2> build"),
        ("zn_k_decode_wideILi2ELi4E", "decode_wide<2> 16 waves"), ("zn_k_decode_wideILi2ELi2E", "decode_wide<2> 8 waves"),

@@ -156,6 +156,8 @@ class ZnLib:
         L.zn_set_legacy_tree_descriptions.argtypes = [ci]
         L.zn_decode_status.restype = ci
         L.zn_decode_status.argtypes = [vp]
+        L.zn_decode_status_chain.restype = ci
+        L.zn_decode_status_chain.argtypes = [ci]
         L.zn_last_fused_chunks.restype = ctypes.c_longlong
         L.zn_last_tail_planes.restype = ctypes.c_longlong
         self._L = L
@@ -472,6 +474,10 @@ class ZnLib:
     def decode_status(self, stream=0):
         """zn_decode_status: wait for `stream`, raise what the last check=False decode call on this device would have raised."""
         self._check(self._L.zn_decode_status(ctypes.c_void_p(stream or None)))
+
+    def decode_status_chain(self, on):
+        """zn_decode_status_chain: while on, this thread's check=False decode calls add their verdict to that of its previous one (one decode_status for all)."""
+        self._check(self._L.zn_decode_status_chain(1 if on else 0))
 
     def last_fused_chunks(self):
         """Chunks of the last decompress_dev call that took the fused single-pass kernel."""

@@ -26,6 +26,7 @@ thread_local std::string t_kernels;
 thread_local int t_status_dev = -1;
 thread_local uint32_t t_status_slot = 0;
 thread_local uint64_t t_status_gen = 0;
+thread_local int t_status_chain = 0;          // zn_decode_status_chain: this thread's unchecked decode calls add to the status slot of its previous one
 
 #define ZN_HIP(call)                                                            \
   do {                                                                          \
@@ -406,6 +407,8 @@ struct DecodeSet {
   bool hinted[3] = {false, false, false};        // … and whether any segment of the plane count has one
   uint64_t pk_of[3] = {0, 0, 0}, k_of[3] = {0, 0, 0}, wg_of[3] = {0, 0, 0}, tail_of[3] = {0, 0, 0};
   bool delta_of[3] = {false, false, false}, rest_ok[3] = {true, true, true};
+  bool inplace_rot_of[3] = {false, false, false};   // … and that segment has the sign rotate (zn_k_alias_rotate goes ahead of the generic kernels)
+  bool inplace_of[3] = {false, false, false};    // some segment's delta base is its destination (xr == dst: the in-place contract of zipnn_hip.h)
   uint64_t total_chunks = 0;
   int wide = 0;
 };
@@ -473,6 +476,7 @@ static int build_segments(const zn_window_item* items, size_t count, DecodeSet& 
     sg.body = (const uint8_t*)it.d_body; sg.body_len = it.body_len; sg.dst = (uint8_t*)it.d_dst;
     sg.xr = it.d_delta ? (const uint8_t*)it.d_delta + (uint64_t)it.chunk_lo * it.chunk : nullptr;
     if (sg.xr) delta_of[q] = true;
+    if (sg.xr && sg.xr == sg.dst) { D.inplace_of[q] = true; if (sg.g.rot) D.inplace_rot_of[q] = true; }
     // (a LARGE call in a geometry the fused kernel takes no chunk of — its rule: whole rows per stream, a 16-byte aligned destination — goes to the generic
     //  KERNELS, which spread it over the whole chip with one wave per plane; the fused kernel's rest instance decodes the odd chunk, or the odd small tensor)
     { const uint64_t unit = 64ull * (sg.g.P == 1 ? 16u : 8u);
@@ -532,14 +536,18 @@ static int launch_segments(const DecodeSet& D, const ZnSeg* d_table, hipStream_t
   }
   if ((rc = ws_acquire(w, stream))) return rc;
   // this call's status slot (status word + the three "left to the generic kernels" counters)
-  const uint32_t slot = (uint32_t)(w.status_gen % ZN_STATUS_SLOTS);
-  w.slot_gen[slot] = ++w.status_gen; w.last_slot = slot;
-  if (!check) { t_status_dev = dev; t_status_slot = slot; t_status_gen = w.status_gen; }
+  // (chained, zn_decode_status_chain: the slot of this thread's previous unchecked call on the device, if it is still that call's — the verdicts add up)
+  const bool chain = !check && t_status_chain && t_status_dev == dev && t_status_gen != 0 && w.slot_gen[t_status_slot] == t_status_gen;
+  const uint32_t slot = chain ? t_status_slot : (uint32_t)(w.status_gen % ZN_STATUS_SLOTS);
+  if (!chain) w.slot_gen[slot] = ++w.status_gen;
+  w.last_slot = slot;
+  if (!check && !chain) { t_status_dev = dev; t_status_slot = slot; t_status_gen = w.status_gen; }
   uint32_t* d_status = (uint32_t*)w.buf[WS_WORDS] + 16 + 4u * slot;
   w.last_K = all_k; w.last_tails = all_tail;
   // status + the three "left to the generic kernels" counters (a wide call: its first kernel zeroes them)
   bool status_zeroed = false;
-  if (!wide || all_tail) { ZN_HIP(hipMemsetAsync(d_status, 0, 4 * sizeof(uint32_t), stream)); status_zeroed = true; }
+  if (chain) { ZN_HIP(hipMemsetAsync(d_status + 1, 0, 3 * sizeof(uint32_t), stream)); status_zeroed = true; }      // (the counters are this call's; the status word is kept)
+  else if (!wide || all_tail) { ZN_HIP(hipMemsetAsync(d_status, 0, 4 * sizeof(uint32_t), stream)); status_zeroed = true; }
   if (all_tail) ZN_HIP(hipMemsetAsync(w.buf[WS_META_A], 0, sync_off + 2u * sizeof(uint32_t) * all_tail, stream));
   if (staged) {
     // the previous batched call may still be reading the pinned staging: wait for it on the host
@@ -605,9 +613,9 @@ static int launch_segments(const DecodeSet& D, const ZnSeg* d_table, hipStream_t
     }
     const bool rest = zn_launch_decode_fused(P, segs[q][0], d_segs, nseg, (uint32_t)wg_of[q], d_done, d_pdone, d_status, (uint32_t)tail_of[q], d_tails,
                                              d_tail_done, delta_of[q], wide, status_zeroed, rest_ok[q] ? d_descs : nullptr,
-                                             tail_of[q] ? (uint32_t*)((uint8_t*)w.buf[WS_META_A] + sync_off) + 2u * tail_base : nullptr, stream);
+                                             tail_of[q] ? (uint32_t*)((uint8_t*)w.buf[WS_META_A] + sync_off) + 2u * tail_base : nullptr, stream, D.inplace_of[q]);
     status_zeroed = true;
-    if (!rest) zn_launch_decode_generic(P, segs[q][0], d_segs, nseg, pk_of[q], k_of[q], d_descs, d_status, d_done, d_pdone, d_tails, d_tail_done, stream);
+    if (!rest) zn_launch_decode_generic(P, segs[q][0], d_segs, nseg, pk_of[q], k_of[q], d_descs, d_status, d_done, d_pdone, d_tails, d_tail_done, stream, D.inplace_rot_of[q]);
   }
   stream = stream_main;
   if (overlap) {
@@ -1628,6 +1636,8 @@ int zn_decompress_multi_dev(const void* body, size_t body_len, int num_buf, int 
 // The device-side status of the last decode call on the current device that was made with check = 0: waits for `stream`, reads the
 // status word that call left in the workspace.  A loader launches its batched decode without the read-back, builds its tensor views
 // while the kernels run, and asks here once at the end.
+int zn_decode_status_chain(int on) { t_status_chain = on ? 1 : 0; return ZN_OK; }
+
 int zn_decode_status(void* stream_) {
   try {
     int dev = 0;

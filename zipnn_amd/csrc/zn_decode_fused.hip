@@ -960,6 +960,9 @@ __global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void ZN_K_DECODE
                                                                   ZnPlaneDesc* __restrict__ descs_rest, uint32_t nchunk_wg, uint32_t merge_per,
                                                                   uint32_t* __restrict__ tailsync ZN_K_HM_PARAMS) {
   ZN_K_HM_CONST
+  // X && REST is the IN-PLACE instance (launches in which some segment's delta base is its destination, include/zipnn_hip.h): the delta instance plus the undo
+  // below.  It has nothing of the rest instance — RST is what REST meant before the combination had a meaning.
+  constexpr bool RST = REST && !X, INPLACE = REST && X;
   constexpr int EPL = (P == 1) ? 16 : 8;
   constexpr uint32_t UNIT = 64u * EPL;
   __shared__ ZnFusedLds L;
@@ -969,7 +972,7 @@ __global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void ZN_K_DECODE
   // tensor t that are through), classify the chunk's planes (the generic path's own item function, every one for itself) and merge its planes into the output
   // (the generic merge's item function, its 64 sub-ranges dealt out) — the two generic launches behind every call of a ragged tensor (20-30 us) are gone.
   // The tail workgroups have the lowest block indices and the merge workgroups are few: the wait is for workgroups that run or have run (and it is bounded).
-  if (REST && tailsync && blockIdx.x >= ntail + nchunk_wg) {
+  if (RST && tailsync && blockIdx.x >= ntail + nchunk_wg) {
     const ZnSeg one_c = one;
     zn_tail_merge_wg<P>(L, one_c, segs, nseg, blockIdx.x - (ntail + nchunk_wg), merge_per, tailsync, descs_rest, status, tail_done, tail_scratch);
     return;
@@ -981,7 +984,7 @@ __global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void ZN_K_DECODE
   if (blockIdx.x < ntail) {
     const ZnSeg one_c = one; uint32_t tail0 = 0;
     zn_decode_tail_wg(L, one_c, segs, nseg, blockIdx.x, tail_scratch, tail_done, status, &tail0);
-    if (REST && tailsync) {                      // (every tail workgroup of the tensor reports, whatever it found: the merge workgroups count them)
+    if (RST && tailsync) {                      // (every tail workgroup of the tensor reports, whatever it found: the merge workgroups count them)
       __syncthreads();
       if (threadIdx.x == 0) { ZN_FLAG_RELEASE(); ZN_FLAG_ADD32(tailsync + 2u * (tail0 / (uint32_t)P), 1u); }
     }
@@ -1006,7 +1009,7 @@ __global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void ZN_K_DECODE
 //  return at once when it is zero)
 // (REST: the chunk is decoded here and now by the generic path's code — its planes by waves 0 .. P-1, each on an LDS instance of its own laid over
 //  this kernel's tables, then the merge by the whole workgroup; the done flag stays 0: "not by the fused kernel")
-#define ZN_REST_CHUNK(c_) do { if constexpr (REST) { \
+#define ZN_REST_CHUNK(c_) do { if constexpr (RST) { \
     static_assert(4u * sizeof(ZnPlanesLds) <= sizeof(ZnFusedLds), "four generic plane decoders fit over the fused kernel's LDS"); \
     __syncthreads(); \
     const ZnSeg one_c_ = one; \
@@ -1072,7 +1075,7 @@ __global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void ZN_K_DECODE
     if (j > 0) __syncthreads();              // the previous chunk's tables are no longer in use
     ZN_PT(21);  // wait for the slowest wave of the previous chunk
     const uint32_t what = zn_uniform(L.what[j]);          // (what comes out of LDS or HBM below is wave-uniform: scalar registers, scalar branches)
-    if (REST && tailsync && what == 0u && S.has_tail && c == g.K - 1u) {              // the partial last chunk: the tail + merge workgroups of this launch
+    if (RST && tailsync && what == 0u && S.has_tail && c == g.K - 1u) {              // the partial last chunk: the tail + merge workgroups of this launch
       if (tid == 0) done[c] = 0; if (tid < (uint32_t)P) pdone[(uint64_t)tid * g.K + c] = 0;
       continue;
     }
@@ -1085,6 +1088,8 @@ __global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void ZN_K_DECODE
       if (p > h && h >= 0 && pl[p].kind == ZN_KIND_HUF) { more |= 1u << p; pl[p].kind = ZN_KIND_RLE; pl[p].off = 0; }
     }
 
+    [[maybe_unused]] bool undo = false;         // INPLACE: the passes below run a second time (see where they give a chunk up)
+  zn_passes_again:
     uint32_t TL = 0;
     const uint8_t* stream = nullptr; uint32_t slen = 0;
     uint32_t h_before = 0, h_mine = 0;       // HM: hint bytes of the streams ahead of this wave's / of its own
@@ -1162,6 +1167,22 @@ __global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void ZN_K_DECODE
     // ---- further Huffman planes (deltas, sparse tensors: every plane compresses): one more pass per plane
     if (HM != 2 && P >= 2 && __builtin_expect(more != 0u, 0)) {      // (further planes are decoded without hints; an index build has no rows to add them to)
       const int r2 = zn_fused_more_passes<P>(L, g, body, body_end, outq, j, more, seg ZN_PT_PASS);
+      // (IN PLACE, xq == outq, the rows of this chunk no longer hold the base the generic path needs: they hold it XORed with the first pass and with the passes
+      //  of the planes ahead of the one given up.  Every one of those passes is a function of the body alone and XORs into what stands there — the same
+      //  passes once more, up to the same refusal, and the rows hold the base again.  The tables of the first plane are parsed again: the later passes overwrote them.)
+      if constexpr (INPLACE) {
+        if (r2 < 0 && !undo && xq != nullptr && xq == outq) {
+          undo = true;
+          __syncthreads();
+          if (wave == 0) {
+            uint8_t* scratch = (uint8_t*)&L.ring[0][0];
+            const ZnWaveStats st0 = zn_wave_read_stats(body + L.plane[j][h].off, L.plane[j][h].csize, body_end, lane, scratch, L.symlist[j], L.rank_start[j], L.sym_start[j], scratch + 512);
+            if (lane == 0) L.st[j] = st0;
+          }
+          __syncthreads();
+          goto zn_passes_again;
+        }
+      }
       if (r2 < 0) { ZN_REST_CHUNK(c); ZN_SET_DONE(c, 0); continue; }   // a later plane this kernel does not take: the generic path redoes the chunk
       ok = ok && r2 > 0;
     }
@@ -1320,7 +1341,7 @@ extern "C" int zn_set_decode_group(int chunks_per_workgroup) {
 
 bool zn_launch_decode_fused(int P, const ZnSeg& one, const ZnSeg* d_segs, uint32_t nseg, uint32_t total_wg,
                             uint8_t* d_done, uint8_t* d_pdone, uint32_t* d_status, uint32_t ntail, uint8_t* d_tail_scratch,
-                            uint8_t* d_tail_done, bool delta, int wide, bool status_zeroed, ZnPlaneDesc* d_descs_rest, uint32_t* d_tailsync, hipStream_t stream) {
+                            uint8_t* d_tail_done, bool delta, int wide, bool status_zeroed, ZnPlaneDesc* d_descs_rest, uint32_t* d_tailsync, hipStream_t stream, bool inplace) {
   // the rest instance: every launch without delta bases (its tile loops run as fast as the plain instance's — measured, 160 MiB .. 4 GiB — and the two generic
   // launches behind it are saved: 256 MiB 128.4 -> 125.9 us, 4 GiB 1514.9 -> 1512.9); partial last chunks (ntail > 0) are finished by merge workgroups at the
   // end of the same launch (d_tailsync: two zeroed words per tensor with a partial chunk); behind the wide kernel, whose launch has the tail workgroups, the merge workgroups of this one find their reports in
@@ -1348,9 +1369,11 @@ bool zn_launch_decode_fused(int P, const ZnSeg& one, const ZnSeg* d_segs, uint32
 #define ZN_GO(P_, X_, R_) hipLaunchKernelGGL((zn_k_decode_fused<P_, X_, R_>), dim3(total_wg), dim3(ZN_F_THREADS), 0, stream, one, d_segs, nseg, d_done, d_pdone, d_status, ntail_wg, d_tail_scratch, d_tail_done, only_pending, d_descs_rest, nchunk_wg, merge_per, d_tailsync)
   if (d_descs_rest) { if (P == 1) ZN_GO(1, false, true); else if (P == 2) ZN_GO(2, false, true); else ZN_GO(4, false, true); }
   else if (!delta) { if (P == 1) ZN_GO(1, false, false); else if (P == 2) ZN_GO(2, false, false); else ZN_GO(4, false, false); }
+  // (in place — a base that is the destination — with more than one plane: the instance that can give a chunk up after its first pass and hand the base back)
+  else if (inplace && P > 1) { if (P == 2) ZN_GO(2, true, true); else ZN_GO(4, true, true); }
   else { if (P == 1) ZN_GO(1, true, false); else if (P == 2) ZN_GO(2, true, false); else ZN_GO(4, true, false); }
 #undef ZN_GO
-  zn_note_kernel(d_descs_rest ? (ntail && !wide ? "zn_k_decode_fused^rest+tail+merge" : "zn_k_decode_fused^rest") : wide ? "zn_k_decode_fused^pending" : delta ? (ntail ? "zn_k_decode_fused^delta+tail" : "zn_k_decode_fused^delta") : (ntail ? "zn_k_decode_fused+tail" : "zn_k_decode_fused"));
+  zn_note_kernel(d_descs_rest ? (ntail && !wide ? "zn_k_decode_fused^rest+tail+merge" : "zn_k_decode_fused^rest") : wide ? "zn_k_decode_fused^pending" : delta ? ((inplace && P > 1) ? (ntail ? "zn_k_decode_fused^delta^inplace+tail" : "zn_k_decode_fused^delta^inplace") : (ntail ? "zn_k_decode_fused^delta+tail" : "zn_k_decode_fused^delta")) : (ntail ? "zn_k_decode_fused+tail" : "zn_k_decode_fused"));
   return d_descs_rest != nullptr;
 }
 #endif   // !ZN_DECODE_HINTED_TU

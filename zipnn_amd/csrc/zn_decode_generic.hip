@@ -7,6 +7,7 @@
 //                        (strided) byte positions of the output — no scratch memory.
 //   zn_k_merge_planes    one workgroup per chunk: fill in the raw / RLE planes from the body,
 //                        undo the sign-bit rotate (in place, word by word), XOR with the delta base if there is one.
+//   zn_k_alias_rotate    only where a delta base IS its destination: prepares those chunks for the two kernels above.
 //
 // Replaces: decompression_chunk_worker (reference csrc/zipnn_core.c:768-861), the metadata
 // parse of py_combine_dtype (:929-1028), HUF_decompress (call site :807) and
@@ -42,7 +43,7 @@ __global__ __launch_bounds__(ZN_WAVE) void zn_k_decode_planes(ZnSeg one, const Z
     for (uint32_t k = 0; k < n; k++) {
       const uint64_t bb = blockIdx.x + (base + todo[k]) * gridDim.x;
       __syncthreads();                         // the tables of the previous item are no longer in use
-      zn_decode_plane_item(L, one, segs, nseg, bb, descs_all, status, tail_done, threadIdx.x);
+      zn_decode_plane_item<true>(L, one, segs, nseg, bb, descs_all, status, tail_done, threadIdx.x);
     }
     __syncthreads();
   }
@@ -67,7 +68,32 @@ __global__ __launch_bounds__(256) void zn_k_merge_planes(ZnSeg one, const ZnSeg*
     const uint32_t n = n_todo;
     for (uint32_t k = 0; k < n; k++) {
       const uint64_t it2 = blockIdx.x + (base + todo[k]) * gridDim.x;
-      zn_merge_chunk_item<P>(one, segs, nseg, it2 / ZN_MERGE_SUB, (uint32_t)(it2 % ZN_MERGE_SUB), descs_all, tails);
+      zn_merge_chunk_item<P, true>(one, segs, nseg, it2 / ZN_MERGE_SUB, (uint32_t)(it2 % ZN_MERGE_SUB), descs_all, tails);
+    }
+    __syncthreads();
+  }
+}
+
+// In-place delta segments (S.xr == S.dst, include/zipnn_hip.h): ahead of the two kernels above, the base words of every chunk the fused kernel left are put
+// into the rotated domain where they stand — the work loop of the merge kernel, over the same chunks.  Launched only when the host saw such a
+// segment with the sign rotate in the launch; every other segment's chunks are passed over.
+template <int P>
+__global__ __launch_bounds__(256) void zn_k_alias_rotate(ZnSeg one, const ZnSeg* __restrict__ segs, uint32_t nseg, uint64_t total,
+                                                         const uint8_t* __restrict__ done_all, const uint32_t* __restrict__ left) {
+  if (left && *left == 0u) return;
+  __shared__ uint32_t n_todo; __shared__ uint16_t todo[256];
+  const uint64_t items = total * ZN_MERGE_SUB;
+  const uint64_t nit = (items > blockIdx.x) ? (items - blockIdx.x + gridDim.x - 1u) / gridDim.x : 0;
+  for (uint64_t base = 0; base < nit; base += 256u) {
+    if (threadIdx.x == 0) n_todo = 0;
+    __syncthreads();
+    const uint64_t i = base + threadIdx.x, it = blockIdx.x + i * gridDim.x;
+    if (i < nit && !(done_all && done_all[it / ZN_MERGE_SUB])) todo[atomicAdd(&n_todo, 1u)] = (uint16_t)threadIdx.x;
+    __syncthreads();
+    const uint32_t n = n_todo;
+    for (uint32_t k = 0; k < n; k++) {
+      const uint64_t it2 = blockIdx.x + (base + todo[k]) * gridDim.x;
+      zn_alias_rotate_item<P>(one, segs, nseg, it2 / ZN_MERGE_SUB, (uint32_t)(it2 % ZN_MERGE_SUB));
     }
     __syncthreads();
   }
@@ -75,11 +101,16 @@ __global__ __launch_bounds__(256) void zn_k_merge_planes(ZnSeg one, const ZnSeg*
 
 void zn_launch_decode_generic(int P, const ZnSeg& one, const ZnSeg* d_segs, uint32_t nseg, uint64_t total_pk, uint64_t total_k,
                               ZnPlaneDesc* d_descs, uint32_t* d_status, const uint8_t* d_done, const uint8_t* d_pdone,
-                              const uint8_t* d_tail_scratch, const uint8_t* d_tail_done, hipStream_t stream) {
+                              const uint8_t* d_tail_scratch, const uint8_t* d_tail_done, hipStream_t stream, bool inplace_rot) {
   if (total_k == 0) return;
   // d_done != null: the fused kernel ran before us and counted the chunks it left in d_status[1 + q]
   const uint32_t* left = d_done ? d_status + 1 + (P == 1 ? 0 : P == 2 ? 1 : 2) : nullptr;
   const uint32_t gp = (uint32_t)(total_pk < 2048u ? total_pk : 2048u), gm = (uint32_t)(total_k * ZN_MERGE_SUB < 1024u ? total_k * ZN_MERGE_SUB : 1024u);
+  if (inplace_rot && P > 1) {
+    if (P == 2) hipLaunchKernelGGL(zn_k_alias_rotate<2>, dim3(gm), dim3(256), 0, stream, one, d_segs, nseg, total_k, d_done, left);
+    else hipLaunchKernelGGL(zn_k_alias_rotate<4>, dim3(gm), dim3(256), 0, stream, one, d_segs, nseg, total_k, d_done, left);
+    zn_note_kernel("zn_k_alias_rotate");
+  }
   hipLaunchKernelGGL(zn_k_decode_planes, dim3(gp), dim3(ZN_WAVE), 0, stream, one, d_segs, nseg, total_pk, d_descs, d_status, d_pdone, d_tail_done, left);
   zn_note_kernel("zn_k_decode_planes");
   if (P == 1) hipLaunchKernelGGL(zn_k_merge_planes<1>, dim3(gm), dim3(256), 0, stream, one, d_segs, nseg, total_k, d_descs, d_done, d_tail_scratch, left);

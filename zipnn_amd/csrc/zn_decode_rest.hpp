@@ -24,9 +24,10 @@ __device__ inline uint64_t zn_window(const uint8_t* base, int32_t bitpos) {
 }
 
 // returns 0 when the stream decodes to exactly `nout` symbols and is fully consumed
-// (symbol i goes to out[i * stride])
+// (symbol i goes to out[i * stride]; A && acc — an in-place delta segment, see zn_decode_plane_item: it is XORed into what stands there)
+template <bool A = false>
 __device__ inline int zn_decode_stream_serial(const uint8_t* src, uint32_t len, uint8_t* out, uint32_t stride, uint32_t nout,
-                                              const uint16_t* lut, uint32_t tl) {
+                                              const uint16_t* lut, uint32_t tl, bool acc = false) {
   if (len == 0 || src[len - 1] == 0) return 1;
   int32_t bitpos = (int32_t)(len - 1u) * 8 + (int32_t)zn_hb32(src[len - 1]);
   uint32_t produced = 0;
@@ -37,7 +38,9 @@ __device__ inline int zn_decode_stream_serial(const uint8_t* src, uint32_t len, 
     while (produced < nout && avail >= (int32_t)tl) {
       const uint32_t e = lut[(uint32_t)(cont >> (64 - tl))];
       const uint32_t nb = e >> 8;
-      out[(uint64_t)produced * stride] = (uint8_t)e; produced++;
+      if (A && acc) out[(uint64_t)produced * stride] ^= (uint8_t)e;
+      else out[(uint64_t)produced * stride] = (uint8_t)e;
+      produced++;
       cont <<= nb; bitpos -= (int32_t)nb; avail -= (int32_t)nb;
     }
   }
@@ -55,6 +58,10 @@ struct ZnPlanesLds {
 
 // one (plane, chunk) = launch-wide desc index b, by ONE WAVE (lane = its lane index; the only synchronisation inside is wave-level, so that
 // several waves of a workgroup may each run an item of their own on an LDS instance of their own)
+// A (the generic KERNELS only — the rest instances of the fused kernel never see a delta base and compile the function as it was): a segment whose delta
+// base IS its destination (S.xr == S.dst, the in-place contract of include/zipnn_hip.h) still holds the base where the symbols go.  zn_k_alias_rotate has put
+// the chunk's base words into the rotated domain; the symbols are XORed into them, and the merge adds the other planes and undoes the rotate once.
+template <bool A = false>
 __device__ inline void zn_decode_plane_item(ZnPlanesLds& L, const ZnSeg& one, const ZnSeg* __restrict__ segs, uint32_t nseg, uint64_t b,
                                             ZnPlaneDesc* __restrict__ descs_all, uint32_t* __restrict__ status,
                                             const uint8_t* __restrict__ tail_done, uint32_t lane, bool classify_only = false, uint32_t* wants_serial = nullptr) {
@@ -115,7 +122,7 @@ __device__ inline void zn_decode_plane_item(ZnPlanesLds& L, const ZnSeg& one, co
           const uint32_t nout = (lane < 3) ? seg : m.plen - 3u * seg;
           // plane byte i of this chunk is output byte i * P + p
           uint8_t* o = dst + c * g.chunk + ((uint64_t)lane * seg) * g.P + p;
-          if (zn_decode_stream_serial(js + so, lens[lane], o, g.P, nout, lut, tl))
+          if (zn_decode_stream_serial<A>(js + so, lens[lane], o, g.P, nout, lut, tl, A && S.xr != nullptr && S.xr == S.dst))
             bad = ZN_DEV_CORRUPT;
         }
       }
@@ -123,6 +130,26 @@ __device__ inline void zn_decode_plane_item(ZnPlanesLds& L, const ZnSeg& one, co
   }
   if (bad) atomicOr(status, bad);
   if (lane == 0) descs[pc] = d;
+}
+
+// ---------------------------------------------------------------------------
+// in place (A): the base words of one not-done chunk go into the rotated domain, where the planes are XORed into them
+// ---------------------------------------------------------------------------
+#define ZN_MERGE_SUB 64u
+template <int P>
+__device__ __forceinline__ void zn_alias_rotate_item(const ZnSeg& one, const ZnSeg* __restrict__ segs, uint32_t nseg, uint64_t b, uint32_t sub) {
+  const ZnSeg S = zn_find_seg<2>(one, segs, nseg, b);
+  const ZnGeom g = S.g;
+  if (S.xr == nullptr || S.xr != S.dst || !g.rot) return;
+  const uint64_t c = b - S.chunk0;
+  uint8_t* out = ZN_GLOBAL_PTR(uint8_t, S.dst) + c * g.chunk;
+  const uint32_t nwords = zn_chunk_len(g, c) / 4u;       // (the words the merge un-rotates: the trailing bytes of a chunk are never rotated)
+  const uint32_t w_lo = (uint32_t)(((uint64_t)nwords * sub) / ZN_MERGE_SUB), w_hi = (uint32_t)(((uint64_t)nwords * (sub + 1u)) / ZN_MERGE_SUB);
+  for (uint32_t wi = w_lo + threadIdx.x; wi < w_hi; wi += blockDim.x) {
+    uint32_t w = zn_ld32(out + 4ull * wi);
+    w = (P == 2) ? zn_rot_fwd16(w) : zn_rot_fwd32(w);
+    for (uint32_t t = 0; t < 4; t++) out[4ull * wi + t] = (uint8_t)(w >> (8 * t));
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -137,8 +164,8 @@ __device__ __forceinline__ uint32_t zn_plane_byte(const ZnPlaneDesc& d, const ui
   return body[d.off + i];
 }
 
-template <int P>
-#define ZN_MERGE_SUB 64u      // a chunk is merged by 64 workgroup-items (one not-done chunk = a partial tail: 250 µs by one workgroup, 45 µs by 16, four byte-gathering iterations per thread by 64)
+template <int P, bool A = false>
+// ZN_MERGE_SUB (above): a chunk is merged by 64 workgroup-items (one not-done chunk = a partial tail: 250 µs by one workgroup, 45 µs by 16, four byte-gathering iterations per thread by 64)
 __device__ __forceinline__ void zn_merge_chunk_item(const ZnSeg& one, const ZnSeg* __restrict__ segs, uint32_t nseg, uint64_t b, uint32_t sub,
                                                     const ZnPlaneDesc* __restrict__ descs_all, const uint8_t* __restrict__ tails, uint32_t nsub = ZN_MERGE_SUB) {
   const ZnSeg S = zn_find_seg<2>(one, segs, nseg, b);
@@ -153,6 +180,29 @@ __device__ __forceinline__ void zn_merge_chunk_item(const ZnSeg& one, const ZnSe
   ZnPlaneDesc d[P];
   for (int p = 0; p < P; p++) d[p] = descs[(uint64_t)p * g.K + c];
   const uint32_t nwords = clen / 4u;
+  if constexpr (A) {
+    // in place (S.xr == S.dst): the chunk holds rot(base) ^ (the symbols of its Huffman planes), trailing clen % 4 bytes unrotated.  The other planes are
+    // XORed in and the rotate is undone once — a bit permutation, so rot_inv(rot(base) ^ planes) = base ^ rot_inv(planes): no separate base term.
+    if (xo == out) {
+      const uint32_t a_lo = (uint32_t)(((uint64_t)nwords * sub) / nsub), a_hi = (uint32_t)(((uint64_t)nwords * (sub + 1u)) / nsub);
+      for (uint32_t wi = a_lo + threadIdx.x; wi < a_hi; wi += blockDim.x) {
+        uint32_t w = 0;
+        for (uint32_t t = 0; t < 4; t++) {
+          const uint32_t j = 4u * wi + t;
+          const ZnPlaneDesc& dd = d[j % P];
+          w |= (dd.kind == ZN_KIND_HUF ? (uint32_t)out[j] : (uint32_t)out[j] ^ zn_plane_byte(dd, body, out, tails, j, j / P)) << (8 * t);
+        }
+        if (g.rot) w = (P == 2) ? zn_rot_inv16(w) : zn_rot_inv32(w);
+        for (uint32_t t = 0; t < 4; t++) out[4ull * wi + t] = (uint8_t)(w >> (8 * t));
+      }
+      if (sub == nsub - 1u && threadIdx.x < (clen & 3u)) {
+        const uint32_t j = 4u * nwords + threadIdx.x;
+        const ZnPlaneDesc& dd = d[j % P];
+        if (dd.kind != ZN_KIND_HUF) out[j] = (uint8_t)((uint32_t)out[j] ^ zn_plane_byte(dd, body, out, tails, j, j / P));
+      }
+      return;
+    }
+  }
   // whole 32-bit words: gather P-way, undo the rotate (applies to clen/4 words — all of them)
   const uint32_t w_lo = (uint32_t)(((uint64_t)nwords * sub) / nsub), w_hi = (uint32_t)(((uint64_t)nwords * (sub + 1u)) / nsub);      // (sub-range `sub` of `nsub`)
   for (uint32_t wi = w_lo + threadIdx.x; wi < w_hi; wi += blockDim.x) {

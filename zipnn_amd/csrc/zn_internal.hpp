@@ -41,9 +41,10 @@ static_assert(sizeof(ZnSeg) == 96, "ZnSeg is a by-value kernel argument and a ta
 // ---- generic decode path (any dtype, any tail) : zn_decode_generic.hip ----
 // descs: Σ P·K entries; status: one device word; d_done: Σ K flags written by the fused kernel.
 // segs == nullptr: the single tensor `one`.  total_pk / total_k: grid sizes (Σ P·K, Σ K).
+// inplace_rot: some segment of the launch has its delta base AT its destination (xr == dst) and the sign rotate — zn_k_alias_rotate goes first
 void zn_launch_decode_generic(int P, const ZnSeg& one, const ZnSeg* d_segs, uint32_t nseg, uint64_t total_pk, uint64_t total_k,
                               ZnPlaneDesc* d_descs, uint32_t* d_status, const uint8_t* d_done, const uint8_t* d_pdone,
-                              const uint8_t* d_tail_scratch, const uint8_t* d_tail_done, hipStream_t stream);
+                              const uint8_t* d_tail_scratch, const uint8_t* d_tail_done, hipStream_t stream, bool inplace_rot = false);
 
 // ---- fused decode path (full chunks; one pass per Huffman plane) : zn_decode_fused.hip ----
 uint32_t zn_decode_fused_group(uint64_t K);     // chunks per workgroup for a tensor of K chunks
@@ -53,7 +54,8 @@ uint32_t zn_decode_fused_group(uint64_t K);     // chunks per workgroup for a te
 // tail_done[i] = 1 where that worked — the generic kernels take it from there.
 bool zn_launch_decode_fused(int P, const ZnSeg& one, const ZnSeg* d_segs, uint32_t nseg, uint32_t total_wg,
                             uint8_t* d_done, uint8_t* d_pdone, uint32_t* d_status, uint32_t ntail, uint8_t* d_tail_scratch,
-                            uint8_t* d_tail_done, bool delta, int wide, bool status_zeroed, ZnPlaneDesc* d_descs_rest, uint32_t* d_tailsync, hipStream_t stream);     // delta: some tensor of the launch has ZnSeg::xr
+                            uint8_t* d_tail_done, bool delta, int wide, bool status_zeroed, ZnPlaneDesc* d_descs_rest, uint32_t* d_tailsync, hipStream_t stream,
+                            bool inplace = false);     // delta: some tensor of the launch has ZnSeg::xr; inplace: … and for some tensor it IS the destination (the in-place instance)
 // d_tailsync (may be null): two zeroed words per tensor with a partial last chunk — with d_descs_rest the launch then finishes those chunks itself (merge workgroups at its end)
 // wide = 4 / 2 (waves per stream): the launch's segments have ncg == 1 and zn_k_decode_wide (zn_decode_wide.hpp, small inputs) goes first;
 // !status_zeroed: … and zeroes the status words (the call's first launch: the caller then leaves out its memset);

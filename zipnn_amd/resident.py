@@ -54,25 +54,34 @@ class _device_of:
 
 
 class _Entry:
-    """One tensor of the store: a frame body in device memory (`body`, with its codec parameters), or the tensor itself (`raw`)."""
-    __slots__ = ("name", "dtype", "shape", "nbytes", "body", "raw", "P", "bits", "byts", "chunk", "hints")
+    """One tensor of the store: a frame body in device memory (`body`, with its codec parameters), or the tensor itself (`raw`).
+    In a variant store (ResidentCheckpoint.from_state_dict(..., base=...)): `delta` is True where the body encodes tensor ^ base, "same" where the tensor's
+    bytes are the base's (no body; `raw` is the base's own tensor where the base holds it plainly) and False otherwise; `base` is what a delta or "same" entry
+    decodes over and `restore` what revert_ puts back — ("tensor", the base's tensor, held by reference) or ("entry", the base store, its entry) — or None."""
+    __slots__ = ("name", "dtype", "shape", "nbytes", "body", "raw", "P", "bits", "byts", "chunk", "hints", "delta", "base", "restore")
 
     def __init__(self, name, dtype, shape, nbytes, body=None, raw=None, params=None):
         self.name, self.dtype, self.shape, self.nbytes, self.body, self.raw = name, dtype, tuple(int(d) for d in shape), int(nbytes), body, raw
         self.hints = None                      # the body's decode hints (ResidentCheckpoint.build_index): a uint8 tensor beside the body, or None
         self.P, self.bits, self.byts, self.chunk = params if params is not None else (0, 0, 0, 0)
+        self.delta, self.base, self.restore = False, None, None
 
     @property
     def compressed(self):
         return self.body is not None
 
     @property
-    def chunks(self):
-        return (self.nbytes + self.chunk - 1) // self.chunk if self.compressed else 0
+    def decoded(self):
+        """Whether reading the tensor runs a decode (a body of its own, or a "same" entry over a base that is compressed itself)."""
+        return self.body is not None or (self.delta == "same" and self.raw is None)
 
-    def window(self, lo, hi, dst_ptr):
-        """-> the item tuple of ZnLib.decompress_window_batch_dev / plan_create for chunks [lo, hi) of this tensor."""
-        return (self.body.data_ptr(), self.body.numel(), self.P, self.bits, self.byts, self.chunk, self.nbytes, lo, hi, dst_ptr)
+    @property
+    def chunks(self):
+        return (self.nbytes + self.chunk - 1) // self.chunk if self.decoded else 0
+
+    def window(self, lo, hi, dst_ptr, delta_ptr=None):
+        """-> the item tuple of ZnLib.decompress_window_batch_dev / plan_create for chunks [lo, hi) of this tensor (delta_ptr: the WHOLE tensor's base)."""
+        return (self.body.data_ptr(), self.body.numel(), self.P, self.bits, self.byts, self.chunk, self.nbytes, lo, hi, dst_ptr, delta_ptr)
 
     def hinted(self, lo, hi, dst_ptr):
         """-> the item of ZnLib.decompress_hinted_batch_dev / plan_create_hinted: the window plus the body's index (None, 0 without one)."""
@@ -95,7 +104,17 @@ class ResidentCheckpoint:
         handle = store.hook(model)                                                   # the model's own forward decodes layer by layer
 
     Tensors that a file stores uncompressed (integers, tensors that did not shrink) stay in the store as plain tensors.  Every decode runs on
-    the current stream of the store's device."""
+    the current stream of the store's device.
+
+    A VARIANT store holds a fine-tune as XOR deltas over a base that is already on the device:
+
+        base = ResidentCheckpoint.from_state_dict(base_sd, "cuda:0", index=True)     # or from_file; or a {name: device tensor} mapping / an nn.Module
+        ft = ResidentCheckpoint.from_state_dict(ft_sd, "cuda:0", base=base)          # bodies encode ft ^ base: a fraction of a plain store
+        ft.get_tensor(n); ft.get_tensors(ns); ft.get_slice(n)[a:b]; ft.plan(ns).run(); ft.hook(model)     # all give the fine-tune's bytes
+        ft.apply_(model)          # tensors that hold the base's values now hold the fine-tune's, in place (XOR is its own inverse) …
+        ft.revert_(model)         # … and the base's again
+        ft.info(n)["delta"]       # True, False or "same"
+    """
 
     def __init__(self, device, entries, held_bytes, keep=()):
         self.device = torch.device(device)
@@ -151,42 +170,149 @@ class ResidentCheckpoint:
             store.build_index()
         return store
 
+    @staticmethod
+    def _base_items(base, dev):
+        """-> {name: ("tensor", tensor) | ("entry", store, entry)} for what from_state_dict accepts as `base`."""
+        if base is None:
+            return {}
+        if isinstance(base, ResidentCheckpoint):
+            if base.device != dev:
+                raise ValueError(f"base: a store on {dev}, not on {base.device}")
+            return {name: (("tensor", e.raw) if e.raw is not None else ("entry", base, e)) for name, e in base._entries.items()}
+        if isinstance(base, torch.nn.Module):
+            items = dict(base.named_parameters())
+            items.update(dict(base.named_buffers()))
+        else:
+            items = dict(base)
+        out = {}
+        for name, t in items.items():
+            t = t.detach()
+            if t.device != dev or not t.is_contiguous():
+                raise ValueError(f"base[{name!r}]: a contiguous tensor on {dev} (plain base tensors are read where they lie)")
+            out[name] = ("tensor", t)
+        return out
+
+    #: from_state_dict(base=...): base tensors are taken (and a resident base decoded) in groups of at most this many bytes
+    _BUILD_GROUP_BYTES = 1 << 30
+
     @classmethod
-    def from_state_dict(cls, sd, device="cuda:0", threshold=0.95, method=None, index=False):
+    def from_state_dict(cls, sd, device="cuda:0", threshold=0.95, method=None, index=False, base=None):
         """Compress the tensors of a state dict on `device` (one batched call) and keep the bodies, trimmed to their lengths and packed at
         256-byte boundaries of one allocation.  A tensor whose body would not be smaller than the tensor itself — and every tensor the codec
-        does not take: integers, float64, empty ones — is kept as it is.  index=True: build_index() on the new store."""
+        does not take: integers, float64, empty ones — is kept as it is.  index=True: build_index() on the new store.
+
+        base: the store becomes a VARIANT of it — another ResidentCheckpoint on the same device (compressed or not, a variant itself), a mapping of
+        names to tensors on the device, or a module (its named parameters and buffers).  A tensor the base has under the same name with the same dtype,
+        shape and frame parameters is also compressed as tensor ^ base (a second batched call) and the smaller of the two bodies is kept, the plain one
+        on a tie; a tensor whose bytes ARE the base's is recorded as "same" and holds nothing.  Decodes combine delta and base on the way out; the
+        variant keeps its base alive.  Plain base tensors are held BY REFERENCE and read at decode time: the caller keeps them at the base's values
+        (apply_ on those very tensors changes what the variant decodes over until revert_).  resident_bytes counts the variant's own memory.
+        Peak memory of the build, beside `sd` on the device: the plain pass's compress arena (as large as the tensors, as without `base`); then the
+        plain bodies and, as they come, the delta bodies — each a trimmed copy out of its arena —, plus per group of at most 1 GiB of tensors (or one
+        larger tensor) the decoded tensors of a resident base and one arena of the group's size; at the end the kept bodies are copied once more into
+        the store's one allocation before the copies are dropped: about twice the bodies for a moment, never a whole second copy of the base."""
         dev = cls._work_device(device)
         lib = _capi.lib()
+        based = cls._base_items(base, dev)
         todo, entries = [], {}
+        coders = {}                            # one ZipNN per dtype: what decides a tensor's frame parameters
+
+        def frame_params(t):
+            if t.dtype not in coders:
+                coders[t.dtype] = ZipNN(input_format="torch", bytearray_dtype=t.dtype, method=method or COMPRESSION_METHOD)
+            return tuple(coders[t.dtype].torch_frame_plan(t)[1:])
         for name, t in sd.items():
             t = t.detach()
             if torch.is_floating_point(t) and t.dtype != torch.float64 and t.numel() > 0 and dtype_from_user(t.dtype) is not None:
-                znn = ZipNN(input_format="torch", bytearray_dtype=t.dtype, method=method or COMPRESSION_METHOD)
-                _, P, bits, byts, chunk = znn.torch_frame_plan(t)
+                P, bits, byts, chunk = frame_params(t)
                 todo.append((name, t.to(dev), (P, bits, byts, chunk)))
             else:
                 entries[name] = _Entry(name, t.dtype, t.shape, t.numel() * t.element_size(), raw=t.to(dev).clone())
+
+        def matches(name, t):                  # the base has this tensor: what revert_ restores from
+            ref = based.get(name)
+            if ref is None:
+                return None
+            b = ref[1] if ref[0] == "tensor" else ref[2]
+            return ref if (b.dtype == t.dtype and tuple(b.shape) == tuple(t.shape)) else None
+
+        def delta_ok(ref, t, prm):             # … with the same frame parameters: what a delta body can be coded over
+            if ref[0] == "tensor":
+                return frame_params(ref[1]) == tuple(prm)
+            be = ref[2]
+            return be.decoded and (be.P, be.bits, be.byts, be.chunk) == tuple(prm)
+
+        def trimmed(bodies):                   # (out of the compress arena, which is as large as the tensors themselves)
+            return [b.clone() for b in bodies]
+
         keep, held = [], 0
         if todo:
             with _device_of(dev):
-                bodies = codec.compress_device_batch(lib, [(codec.flat_bytes(t), P, bits, byts, chunk, float(threshold)) for (_, t, (P, bits, byts, chunk)) in todo])
-            kept = [(name, t, prm, b) for (name, t, prm), b in zip(todo, bodies) if b.numel() < t.numel() * t.element_size()]
+                plain = trimmed(codec.compress_device_batch(lib, [(codec.flat_bytes(t), P, bits, byts, chunk, float(threshold)) for (_, t, (P, bits, byts, chunk)) in todo]))
+                refs = [matches(name, t) for (name, t, _) in todo]
+                cand = [i for i, ((name, t, prm), ref) in enumerate(zip(todo, refs)) if ref is not None and delta_ok(ref, t, prm)]
+                dbody, same = {}, set()
+                # in groups of at most _BUILD_GROUP_BYTES of base bytes: plain base tensors are read where they lie, a resident base's tensors are decoded
+                # a group at a time (never the whole base at once), the group's "is it the base's bytes" flags come back in one read
+                groups, cur, size = [], [], 0
+                for i in cand:
+                    nb = todo[i][1].numel() * todo[i][1].element_size()
+                    if cur and size + nb > cls._BUILD_GROUP_BYTES:
+                        groups.append(cur)
+                        cur, size = [], 0
+                    cur.append(i)
+                    size += nb
+                if cur:
+                    groups.append(cur)
+                for grp in groups:
+                    via = [todo[i][0] for i in grp if refs[i][0] == "entry"]
+                    decoded = base.get_tensors(via) if via else {}
+                    flats = {i: codec.flat_bytes(refs[i][1] if refs[i][0] == "tensor" else decoded[todo[i][0]]) for i in grp}
+                    eq = torch.stack([(codec.flat_bytes(todo[i][1]) == flats[i]).all() for i in grp]).tolist()
+                    same.update(i for i, e in zip(grp, eq) if e)
+                    rest = [i for i in grp if i not in same]
+                    if rest:
+                        got = trimmed(codec.compress_device_batch(lib, [(codec.flat_bytes(todo[i][1]),) + tuple(todo[i][2]) + (float(threshold), flats[i]) for i in rest]))
+                        dbody.update(zip(rest, got))
+                    del flats, decoded
+            kept = []                              # (index, body, is a delta body)
+            for i, (name, t, prm) in enumerate(todo):
+                if i in same:
+                    continue
+                b, is_delta = plain[i], False
+                if i in dbody and dbody[i].numel() < b.numel():        # (a tie goes to the plain body)
+                    b, is_delta = dbody[i], True
+                if b.numel() < t.numel() * t.element_size():
+                    kept.append((i, b, is_delta))
             offs, o = [], 0
-            for (_, _, _, b) in kept:
+            for (_, b, _) in kept:
                 offs.append(o)
                 o += _round_up(b.numel())
             packed = torch.empty(max(o, 1), dtype=torch.uint8, device=dev)
-            for (name, t, prm, b), off in zip(kept, offs):
+            for (i, b, is_delta), off in zip(kept, offs):
+                name, t, prm = todo[i]
                 packed[off:off + b.numel()].copy_(b)
-                entries[name] = _Entry(name, t.dtype, t.shape, t.numel() * t.element_size(), body=packed[off:off + b.numel()], params=prm)
-            for (name, t, prm) in todo:
-                if name not in entries:
+                e = entries[name] = _Entry(name, t.dtype, t.shape, t.numel() * t.element_size(), body=packed[off:off + b.numel()], params=prm)
+                if is_delta:
+                    e.delta, e.base = True, refs[i]
+            for i, (name, t, prm) in enumerate(todo):
+                if i in same:                      # nothing of its own: the base's tensor itself, or a decode of the base's body
+                    ref = refs[i]
+                    e = entries[name] = _Entry(name, t.dtype, t.shape, t.numel() * t.element_size(), raw=ref[1] if ref[0] == "tensor" else None, params=prm)
+                    e.delta, e.base = "same", ref
+                elif name not in entries:
                     entries[name] = _Entry(name, t.dtype, t.shape, t.numel() * t.element_size(), raw=t.clone())
+            for (name, t, _), ref in zip(todo, refs):
+                entries[name].restore = ref
             keep.append(packed)
             held += o
-            del bodies                         # (the compress arena — as large as the tensors themselves — goes back to the allocator)
-        held += sum(e.nbytes for e in entries.values() if not e.compressed)
+            del plain, dbody                   # (the bodies not kept go back to the allocator)
+        for name, t in sd.items():
+            if entries[name].restore is None:
+                entries[name].restore = matches(name, t.detach())
+        held += sum(e.nbytes for e in entries.values() if not e.compressed and e.delta != "same")
+        if base is not None:
+            keep.append(base)
         store = cls(dev, [entries[name] for name in sd.keys()], held, keep=keep)
         if index:
             store.build_index()
@@ -204,12 +330,12 @@ class ResidentCheckpoint:
         hook: no further arguments) starts them there instead of finding them by speculation.  The hints sit beside the bodies in device memory,
         never in them, and are advice: the decoded bytes are the same with and without.  names: the tensors to index (default: every compressed
         one); a dtype that measured no gain is left out unless all_dtypes is set.  Tensors already indexed keep their index; plans and hooks made
-        before this call go on decoding without."""
+        before this call go on decoding without.  The delta bodies of a variant store get none: a launch with a delta base reads no hints."""
         lib = _capi.lib()
         todo = []
         for name in (self.keys() if names is None else names):
             e = self._entries[name]
-            if e.compressed and e.nbytes and e.hints is None and (all_dtypes or e.dtype in self.INDEX_DTYPES):
+            if e.compressed and e.delta is False and e.nbytes and e.hints is None and (all_dtypes or e.dtype in self.INDEX_DTYPES):
                 todo.append(e)
         if not todo:
             return 0
@@ -241,14 +367,67 @@ class ResidentCheckpoint:
         """Bytes of device memory the index holds (part of resident_bytes)."""
         return self._index_bytes
 
-    def _decode(self, work, check):
-        """work: [(entry, chunk_lo, chunk_hi, dst_ptr)] -> one batched decode on the current stream, hinted when an entry has an index."""
+    def _launch_sets(self, work, keep=None):
+        """work: [(entry, chunk_lo, chunk_hi, flat uint8 destination of the window)] -> the batched calls that fill the destinations, in the order they
+        must run on one stream: [("hinted" | "window", items)].  A plain entry: one window item.  A delta entry over a plain base tensor: the item with
+        d_delta at that tensor (the library offsets it to the window).  Over a resident base: the BASE's own sets decode the same chunk window into the
+        destination first — hinted if the base has an index, through its own base if it is a variant itself — and the delta's window then runs IN PLACE over
+        it (d_dst == d_delta + chunk_lo * chunk, include/zipnn_hip.h).  A "same" entry is the base's decode alone.  keep: a list that receives what
+        the items refer to by address."""
+        keep = keep if keep is not None else []
+
+        def ptr(dst):                              # (a destination may also be given by its address)
+            return dst if isinstance(dst, int) else dst.data_ptr()
+        via, plain, delta = {}, [], []
+        for e, lo, hi, dst in work:
+            if e.delta is False:
+                plain.append((e, lo, hi, dst))
+                continue
+            if e.base[0] == "tensor":                  # (a delta entry: "same" over a plain tensor is that tensor, never work)
+                bt = codec.flat_bytes(e.base[1])
+                keep.append(bt)
+                delta.append(e.window(lo, hi, ptr(dst), bt.data_ptr()))
+            else:
+                _, bstore, be = e.base
+                via.setdefault(id(bstore), (bstore, []))[1].append((be, lo, hi, dst))
+                if e.delta is True:
+                    delta.append(e.window(lo, hi, ptr(dst), ptr(dst) - lo * e.chunk))
+        sets = []
+        for bstore, w in via.values():
+            sets += bstore._launch_sets(w, keep)
+        if plain:
+            if any(e.hints is not None for e, _, _, _ in plain):
+                keep += [e.hints for e, _, _, _ in plain if e.hints is not None]
+                sets.append(("hinted", [e.hinted(lo, hi, ptr(dst)) for e, lo, hi, dst in plain]))
+            else:
+                sets.append(("window", [e.window(lo, hi, ptr(dst)) for e, lo, hi, dst in plain]))
+        if delta:
+            sets.append(("window", delta))
+        keep += [dst for _, _, _, dst in work if not isinstance(dst, int)]
+        return sets
+
+    def _run_sets(self, sets, check):
+        """The calls of _launch_sets, in order, on the current stream.  check=False: the sets behind the first add their verdict to the first's
+        (zn_decode_status_chain), so that status() speaks for all of them."""
         lib = _capi.lib()
         with _device_of(self.device):
-            if any(e.hints is not None for e, _, _, _ in work):
-                lib.decompress_hinted_batch_dev([e.hinted(lo, hi, dp) for e, lo, hi, dp in work], _stream_of(self.device), check)
-            else:
-                lib.decompress_window_batch_dev([e.window(lo, hi, dp) for e, lo, hi, dp in work], _stream_of(self.device), check)
+            stream = _stream_of(self.device)
+            try:
+                for i, (kind, items) in enumerate(sets):
+                    if i == 1 and not check:
+                        lib.decode_status_chain(True)
+                    if kind == "hinted":
+                        lib.decompress_hinted_batch_dev(items, stream, check)
+                    else:
+                        lib.decompress_window_batch_dev(items, stream, check)
+            finally:
+                if len(sets) > 1 and not check:
+                    lib.decode_status_chain(False)
+
+    def _decode(self, work, check):
+        """work: [(entry, chunk_lo, chunk_hi, flat uint8 destination)] -> batched decodes on the current stream, hinted where an entry has an index; one
+        launch set for a plain store, base + delta for a variant (_launch_sets)."""
+        self._run_sets(self._launch_sets(work), check)
 
     # ---- introspection --------------------------------------------------------------------------------------------------------
     def keys(self):
@@ -262,8 +441,9 @@ class ResidentCheckpoint:
 
     def info(self, name):
         e = self._entries[name]
-        return {"shape": list(e.shape), "dtype": e.dtype, "nbytes": e.nbytes, "compressed": e.compressed,
-                "resident_bytes": e.body.numel() if e.compressed else e.nbytes, "index_bytes": e.hints.numel() if e.hints is not None else 0}
+        return {"shape": list(e.shape), "dtype": e.dtype, "nbytes": e.nbytes, "compressed": e.compressed, "delta": e.delta,
+                "resident_bytes": e.body.numel() if e.compressed else (0 if e.delta == "same" else e.nbytes),
+                "index_bytes": e.hints.numel() if e.hints is not None else 0}
 
     @property
     def nbytes(self):
@@ -284,7 +464,7 @@ class ResidentCheckpoint:
         offs, o = {}, 0
         for name in names:
             e = self._entries[name]
-            if e.compressed and name not in offs:
+            if e.decoded and name not in offs:
                 offs[name] = o
                 o += _round_up(e.nbytes)
         return offs, o
@@ -300,7 +480,7 @@ class ResidentCheckpoint:
         views, work = {}, []
         for name in names:
             e = self._entries[name]
-            if not e.compressed:
+            if not e.decoded:
                 views[name] = e.raw
             elif name not in views:
                 flat = into[offs[name]: offs[name] + e.nbytes]
@@ -313,12 +493,12 @@ class ResidentCheckpoint:
         e = self._entries[name]
         if out is not None and (out.dtype != e.dtype or tuple(out.shape) != e.shape or out.device != self.device or not out.is_contiguous()):
             raise ValueError(f"out: a contiguous {e.dtype} tensor of shape {list(e.shape)} on {self.device}")
-        if not e.compressed:
+        if not e.decoded:
             return e.raw.clone() if out is None else out.copy_(e.raw)
         if out is None:
             out = torch.empty(e.shape, dtype=e.dtype, device=self.device)
         if e.nbytes:
-            self._decode([(e, 0, e.chunks, out.data_ptr())], check)
+            self._decode([(e, 0, e.chunks, codec.flat_bytes(out))], check)
         return out
 
     def get_tensors(self, names, into=None, check=True):
@@ -327,7 +507,7 @@ class ResidentCheckpoint:
         they are (views of the store: do not write to them)."""
         views, work = self._destinations(names, into)
         if work:
-            self._decode([(e, 0, e.chunks, flat.data_ptr()) for e, flat in work], check)
+            self._decode([(e, 0, e.chunks, flat) for e, flat in work], check)
         return views
 
     def get_slice(self, name):
@@ -342,6 +522,76 @@ class ResidentCheckpoint:
         """Wait for the stream and raise what the last check=False decode on this device would have raised (zn_decode_status)."""
         with _device_of(self.device):
             _capi.lib().decode_status(_stream_of(self.device, stream))
+
+    # ---- a variant applied to live weights ------------------------------------------------------------------------------------
+    def _targets(self, target):
+        """target: a module (named parameters and buffers) or a mapping -> [(entry, tensor)] for the names the store has."""
+        if isinstance(target, torch.nn.Module):
+            items = dict(target.named_parameters())
+            items.update(dict(target.named_buffers()))
+        else:
+            items = dict(target)
+        out = []
+        for name, t in items.items():
+            e = self._entries.get(name)
+            if e is None:
+                continue
+            t = t.detach()
+            if t.dtype != e.dtype or tuple(t.shape) != e.shape or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"{name}: a contiguous {e.dtype} tensor of shape {list(e.shape)} on {self.device}")
+            out.append((e, t))
+        return out
+
+    def apply_(self, target, check=True):
+        """Turn live BASE weights into the fine-tune's, in place: `target` is a module or a mapping of names to contiguous tensors on the store's device that
+        hold the base's values.  Delta entries are XORed over them by an in-place decode (d_dst == d_delta, include/zipnn_hip.h) — no second copy of the
+        weights, no read of the base —, plain entries are overwritten, "same" entries are left alone; one batched launch set on the current stream.
+        Nothing is tracked: applying twice (or to tensors that do not hold the base) XORs the delta in twice and is the caller's mistake.  If `target` is
+        the very tensors this store holds as its plain base, the store decodes wrong values until revert_.  -> the names changed."""
+        work, inplace, done = [], [], []
+        for e, t in self._targets(target):
+            if e.delta == "same" or not e.nbytes:
+                continue
+            if e.delta is True:
+                inplace.append(e.window(0, e.chunks, t.data_ptr(), t.data_ptr()))
+            elif e.compressed:
+                work.append((e, 0, e.chunks, codec.flat_bytes(t)))
+            else:
+                t.copy_(e.raw)
+            done.append(e.name)
+        sets = self._launch_sets(work)
+        if inplace:
+            sets.append(("window", inplace))
+        self._run_sets(sets, check)
+        return done
+
+    def revert_(self, target, check=True):
+        """The inverse of apply_: delta entries by the same in-place call again (XOR is its own inverse), plain entries restored from the base — its
+        tensor copied, or its resident body decoded — where the base has the tensor with the same dtype and shape.  -> the names that could NOT be
+        reverted (plain entries with nothing to restore from: they stay as they are).  Reverting what was not applied is the caller's mistake."""
+        work, inplace, stay, via = [], [], [], {}
+        for e, t in self._targets(target):
+            if e.delta == "same" or not e.nbytes:
+                continue
+            if e.delta is True:
+                inplace.append(e.window(0, e.chunks, t.data_ptr(), t.data_ptr()))
+            elif e.restore is None:
+                stay.append(e.name)
+            elif e.restore[0] == "tensor":
+                if e.restore[1].data_ptr() == t.data_ptr():          # (the base's tensor IS the target: its values are gone)
+                    stay.append(e.name)
+                else:
+                    t.copy_(e.restore[1])
+            else:
+                _, bstore, be = e.restore
+                via.setdefault(id(bstore), (bstore, []))[1].append((be, 0, be.chunks, codec.flat_bytes(t)))
+        sets = []
+        for bstore, w in via.values():
+            sets += bstore._launch_sets(w)
+        if inplace:
+            sets.append(("window", inplace))
+        self._run_sets(sets, check)
+        return stay
 
     # ---- model integration ----------------------------------------------------------------------------------------------------
     def hook(self, model, modules=None):
@@ -369,7 +619,7 @@ class ResidentSlice:
 
     def __getitem__(self, idx):
         e, dev = self._e, self._s.device
-        if not e.compressed:
+        if not e.decoded:
             self.last_chunk_range = (0, 0)
             return e.raw[idx]
         n, shape, chunk = e.nbytes, e.shape, e.chunk
@@ -382,7 +632,7 @@ class ResidentSlice:
             self.last_chunk_range = (c_lo, c_hi)
             base = c_lo * chunk
             buf = torch.empty(min(c_hi * chunk, n) - base, dtype=torch.uint8, device=dev)      # (torch's allocator orders the block's reuse on the current stream: the decode runs there)
-            self._s._decode([(e, c_lo, c_hi, buf.data_ptr())], False)
+            self._s._decode([(e, c_lo, c_hi, buf)], False)
             t = buf[byte_lo - base: byte_hi - base].view(e.dtype).reshape(() if scalar else (b - a,) + shape[1:])
         return t[sel] if sel else t
 
@@ -391,27 +641,43 @@ class ResidentPlan:
     """`ResidentCheckpoint.plan(names, into=None)`: a zn_plan plus the buffer it decodes into.  Everything a batched decode works out on the
     host is done once, here; `run()` only launches — it neither waits for earlier device work nor copies anything to the device, so the decode
     of the next layer can be enqueued while this one still runs.  `tensors` are the views the runs fill; `status()` waits and raises what a
-    checked decode would have raised; `close()` frees the plan (the store must outlive it)."""
+    checked decode would have raised; `close()` frees the plan (the store must outlive it).  The plan of a variant store over a resident base holds
+    zn_plans of its own and of its base — the base's decode, then the delta windows in place over it —, launched back to back; their verdicts are
+    chained (zn_decode_status_chain), so `status()` speaks for the whole run."""
 
     def __init__(self, store, names, into=None):
         self._store, self._lib = store, _capi.lib()
         self.tensors, work = store._destinations(names, into)
-        self._keep = [flat for _, flat in work]
+        self._keep = []
         self._stream = None
-        self._h = None
+        self._hs = None
+        sets = store._launch_sets([(e, 0, e.chunks, flat) for e, flat in work], self._keep)
         with _device_of(store.device):
-            if any(e.hints is not None for e, _ in work):
-                self._keep += [e.hints for e, _ in work if e.hints is not None]
-                self._h = self._lib.plan_create_hinted([e.hinted(0, e.chunks, flat.data_ptr()) for e, flat in work])
-            else:
-                self._h = self._lib.plan_create([e.window(0, e.chunks, flat.data_ptr()) for e, flat in work])
+            # (a plain store: one zn_plan, as ever; a variant over a resident base: the base's plan, then the plan of the delta windows that run in place over
+            #  what it decoded — run() launches them back to back on one stream)
+            hs = []
+            try:
+                for kind, items in (sets or [("window", [])]):
+                    hs.append(self._lib.plan_create_hinted(items) if kind == "hinted" else self._lib.plan_create(items))
+            except Exception:
+                for h in hs:
+                    self._lib.plan_destroy(h)
+                raise
+            self._hs = hs
 
     def run(self, stream=None):
-        if self._h is None:
+        if self._hs is None:
             raise RuntimeError("the plan is closed")
         self._stream = _stream_of(self._store.device, stream)
         with _device_of(self._store.device):
-            self._lib.plan_run(self._h, self._stream, False)
+            try:
+                for i, h in enumerate(self._hs):
+                    if i == 1:
+                        self._lib.decode_status_chain(True)       # (the later plans add their verdict to the first one's: status() speaks for the whole run)
+                    self._lib.plan_run(h, self._stream, False)
+            finally:
+                if len(self._hs) > 1:
+                    self._lib.decode_status_chain(False)
         return self.tensors
 
     def status(self):
@@ -419,9 +685,10 @@ class ResidentPlan:
             self._lib.decode_status(self._stream if self._stream is not None else _stream_of(self._store.device))
 
     def close(self):
-        if self._h is not None:
-            h, self._h = self._h, None
-            self._lib.plan_destroy(h)
+        if self._hs is not None:
+            hs, self._hs = self._hs, None
+            for h in hs:
+                self._lib.plan_destroy(h)
 
     def __del__(self):
         try:
