@@ -244,6 +244,31 @@ int zn_decompress_range_dev(const void* body, size_t body_len, int num_buf, int 
 int zn_merge_range_bodies(const void* const* bodies, const size_t* body_lens, const size_t* num_chunks, int nparts, int num_buf,
                           void* dst, size_t dst_cap, size_t* dst_len);
 
+/* CONTENT DIGESTS ("zn64-1").  The frame format carries no checksums, and a damaged raw plane decodes cleanly to wrong bytes: a digest of the DECODED bytes
+ * is what tells.  It is an error-detecting code, NOT a cryptographic hash: it catches damage, not an adversary.  The definition (all arithmetic unsigned, wrapping):
+ *
+ *   fmix32(x): x ^= x>>16; x *= 0x85EBCA6B; x ^= x>>13; x *= 0xC2B2AE35; x ^= x>>16                             (mod 2^32)
+ *   mix64(z):  z ^= z>>30; z *= 0xBF58476D1CE4E5B9; z ^= z>>27; z *= 0x94D049BB133111EB; z ^= z>>31             (mod 2^64)
+ *   G = 0x9E3779B97F4A7C15
+ *   bytes b[0..n), zero-padded to a multiple of 4; w_j = little-endian 32-bit word j, counted from the FIRST BYTE (not from an aligned address)
+ *   block c = words [65536 c, 65536 (c+1))                 -- 256 KiB of data, whatever the frame's chunk size or dtype
+ *   B_c = sum_i (u64)w_{65536 c + i} * (u64)fmix32(i + 1)                                                           (mod 2^64)
+ *   D   = mix64(n + G) + sum_c mix64(B_c + (c + 1) G)                                                               (mod 2^64)
+ *
+ * D("") = 0xe220a8397b1dcdaf, D("\x01") = 0x947511c5412f4857.  Inside a block every change of one word and every swap of two words changes B_c (a nonzero
+ * difference below 2^32 times a nonzero key difference below 2^32 cannot vanish mod 2^64; fmix32 is a bijection and never 0 on 1..65536); block order and
+ * length enter through c and n.  Blocks combine by a commutative sum: every schedule gives the same value.
+ *
+ * zn_digest_batch_dev: `count` byte ranges in device memory (any byte address, any length, ragged) -> d_out[i] = D(item i), `count` 8-byte-aligned device
+ * slots; one launch for the whole batch on `stream`, NO host wait for the result (read d_out behind the stream).  A call with count > 1 stages its item table in
+ * the pinned buffer the batched decode calls use, and like them waits on the host until the previous batched call on the device has read it; a single item travels
+ * as a kernel argument and waits for nothing.  count == 0 and n == 0 are valid; a null
+ * d_src with n > 0 (or a null d_out) is ZN_E_ARG.  The kernel reads aligned 16-byte granules and only those that hold a byte of the item.
+ * zn_digest_host: the same value by a scalar loop on the host, for host buffers and files. */
+typedef struct zn_digest_item { const void* d_src; size_t n; } zn_digest_item;
+int zn_digest_batch_dev(const zn_digest_item* items, size_t count, unsigned long long* d_out, void* stream);
+int zn_digest_host(const void* src, size_t n, unsigned long long* out);
+
 /* Plumbing for callers that keep the tensors in HBM but hold pageable host buffers (files, Python bytes): the same
  * pinned, multi-threaded transfer the host-buffer entry points above use internally (zipnn_amd/csrc/zn_host_pipe.hpp),
  * on the current device; returns when the n bytes have arrived.  No reference counterpart — the reference's buffers

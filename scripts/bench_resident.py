@@ -20,6 +20,11 @@ step, so that low mantissa bits change everywhere:
   k  per fine-tune: variant resident bytes against a plain store of the same tensors; plan.run of one block from the plain store, from a variant over plain
      base tensors and from a variant over a resident base, interleaved (A B C A B C: the plain store's two runs are the A/A spread); apply_ + revert_ of
      one block; store build times
+--digest: content digests instead ("zn64-1"), into profiles/resident_digest.{json,txt}:
+  m  one 1 GiB device tensor digested where it lies, 16-byte aligned and at a +1 byte offset, interleaved with plan.run decoding a 1 GiB bf16 N(0, 0.02)
+     tensor in the same process (decode digest decode digest: the decode's two runs are the A/A spread, and the decode is the yardstick — a verify that costs
+     more than the decode it follows is not worth having); a ragged batch of 291 tensors (the Llama-3-8B tensor list at a quarter of its widths, packed back
+     to back at whatever byte address they fall on) in one launch; store.verify() on the four-block store of leg b
 """
 import argparse
 import json
@@ -34,6 +39,7 @@ sys.path.insert(0, ROOT)
 LEG_SECONDS = {"a": 240, "b": 240, "c": 300, "d": 240, "e": 300}
 INDEX_LEG_SECONDS = {"i": 420, "j": 300}
 DELTA_LEG_SECONDS = {"k": 420}
+DIGEST_LEG_SECONDS = {"m": 420}
 CH = 256 * 1024
 
 
@@ -364,6 +370,114 @@ def leg_k(args):
     return res
 
 
+def leg_m(args):
+    import torch
+    import bench
+    from zipnn_amd import ResidentCheckpoint, _capi, codec
+    lib = _capi.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    n = 1 << 30
+    g = torch.Generator(device="cuda"); g.manual_seed(17)
+    x = (torch.randn(n // 2, generator=g, device="cuda") * 0.02).to(torch.bfloat16)
+    store = ResidentCheckpoint.from_state_dict({"x": x}, "cuda:0", digests=True)
+    plan = store.plan(["x"])
+    buf = torch.empty(n + 256, dtype=torch.uint8, device="cuda")
+    a = (-buf.data_ptr()) % 256
+    aligned, shifted = buf[a:a + n], buf[a + 1:a + 1 + n]
+    aligned.copy_(x.view(torch.uint8))
+    out = torch.zeros(1, dtype=torch.int64, device="cuda")
+    want = store.digests()["x"]
+    res = {"bytes": n, "decode_ms": [], "digest_aligned_ms": []}
+    for _ in range(2):                                    # A B A B
+        res["decode_ms"].append(_events_ms(plan.run, args.reps)["median_ms"])
+        plan.status()
+        assert _same(plan.tensors["x"], x)
+        res["decode_kernels"] = _capi_kernels()
+        res["digest_aligned_ms"].append(_events_ms(lambda: codec.digest_device_batch(lib, [aligned], st, out=out), args.reps)["median_ms"])
+        assert codec.digests_to_ints(out) == [want]
+    shifted.copy_(x.view(torch.uint8))
+    assert shifted.data_ptr() % 16 == 1
+    res["digest_plus1_ms"] = _events_ms(lambda: codec.digest_device_batch(lib, [shifted], st, out=out), args.reps)["median_ms"]
+    assert codec.digests_to_ints(out) == [want]
+    res["digest_kernels"] = _capi_kernels()
+    torch.cuda.synchronize(); t0 = time.perf_counter(); host = lib.digest_host(x[:1 << 26].view(torch.uint8).cpu().numpy()); res["host_ms_per_128MiB"] = (time.perf_counter() - t0) * 1e3
+    assert host == codec.digests_to_ints(codec.digest_device_batch(lib, [shifted[:1 << 27]]))[0]      # (the buffer now holds the tensor from +1 on)
+    d, h = res["decode_ms"], res["digest_aligned_ms"]
+    res["aa_spread"] = abs(d[0] - d[1]) / min(d)
+    res["verdict_ok"] = (sum(h) / 2) <= (sum(d) / 2) * (1.0 + res["aa_spread"])
+    plan.close()
+    del store, plan, x, buf, aligned, shifted
+    torch.cuda.empty_cache()
+    # a ragged batch: the 291 tensors of the Llama-3-8B list at a quarter of its widths, bf16, back to back from byte 3 of one buffer
+    sizes = []
+    for _, shape, _l in bench.llama8b_shapes(hidden=1024, inter=3584, vocab=32064):
+        k = 2
+        for dd in shape:
+            k *= dd
+        sizes.append(k + (len(sizes) % 3))                # (… and not all of them even)
+    total = sum(sizes) + 64
+    rag = torch.randint(0, 256, (total,), dtype=torch.uint8, device="cuda", generator=g)
+    flats, o = [], 3
+    for k in sizes:
+        flats.append(rag[o:o + k]); o += k
+    outs = torch.zeros(len(flats), dtype=torch.int64, device="cuda")
+    tb = _events_ms(lambda: codec.digest_device_batch(lib, flats, st, out=outs), args.reps)
+    got = codec.digests_to_ints(outs)
+    for i in (0, 1, 5, 8, 290):
+        assert got[i] == lib.digest_host(flats[i].cpu().numpy()), i
+    ts = []
+    for _ in range(args.reps):
+        torch.cuda.synchronize(); t0 = time.perf_counter(); codec.digest_device_batch(lib, flats, st, out=outs); ts.append((time.perf_counter() - t0) * 1e6)
+    res["ragged"] = {"tensors": len(flats), "bytes": sum(sizes), "median_ms": tb["median_ms"], "gb_per_s": sum(sizes) / tb["median_ms"] / 1e6, "enqueue_us": statistics.median(ts)}
+    del rag, flats
+    torch.cuda.empty_cache()
+    # store.verify() on the four-block store: against the plan.run of its blocks
+    sd, per = _blocks(args.layers)
+    bstore = ResidentCheckpoint.from_state_dict(sd, "cuda:0", digests=True)
+    assert all(bstore.verify().values())
+    ts = []
+    for _ in range(5):
+        torch.cuda.synchronize(); t0 = time.perf_counter(); bstore.verify(); ts.append((time.perf_counter() - t0) * 1e3)
+    scratch = torch.empty(max(bstore.scratch_bytes(nm) for nm in per), dtype=torch.uint8, device="cuda")
+    dec = 0.0
+    for names in per:
+        p = bstore.plan(names, into=scratch)
+        dec += _events_ms(p.run, args.reps)["median_ms"]
+        p.close()
+    res["verify"] = {"layers": args.layers, "tensors": len(sd), "bytes": bstore.nbytes, "verify_wall_ms": statistics.median(ts), "plan_run_all_blocks_ms": dec}
+    return res
+
+
+def main_digest(args):
+    results = {}
+    for leg, limit in DIGEST_LEG_SECONDS.items():
+        p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--layers", str(args.layers), "--reps", str(args.reps)],
+                           capture_output=True, text=True)
+        line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+        if p.returncode != 0 or not line:
+            print(f"leg {leg} failed (exit {p.returncode}); nothing further is started\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}")
+            return 1
+        results[leg] = json.loads(line[0][7:])
+        print(f"leg {leg}: ok", flush=True)
+    out = args.out if args.out != os.path.join(ROOT, "profiles", "resident_decode") else os.path.join(ROOT, "profiles", "resident_digest")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    json.dump(results, open(out + ".json", "w"), indent=1)
+    m = results["m"]
+    d, h = m["decode_ms"], m["digest_aligned_ms"]
+    gbs = lambda ms: m["bytes"] / ms / 1e6      # noqa: E731
+    lines = ["content digest probe (zn64-1, zn_k_digest): device events, median ms; every digest checked against the store's / the host function's",
+             f"1 GiB bf16 N(0, 0.02), interleaved: plan.run decode {d[0]:.4f} / {d[1]:.4f} ms (A/A spread {100 * m['aa_spread']:.1f} %)   [{m['decode_kernels']}]",
+             f"    digest, 16-byte aligned {h[0]:.4f} / {h[1]:.4f} ms ({gbs(sum(h) / 2):.0f} GB/s); at +1 byte {m['digest_plus1_ms']:.4f} ms ({gbs(m['digest_plus1_ms']):.0f} GB/s)   [{m['digest_kernels']}]",
+             f"    verdict (aligned digest no slower than the decode, within the decode's A/A spread): {'MET' if m['verdict_ok'] else 'MISSED'}",
+             f"    zn_digest_host, 128 MiB: {m['host_ms_per_128MiB']:.1f} ms",
+             f"ragged batch, {m['ragged']['tensors']} tensors, {m['ragged']['bytes']} B, one launch: {m['ragged']['median_ms']:.4f} ms ({m['ragged']['gb_per_s']:.0f} GB/s), host time to enqueue {m['ragged']['enqueue_us']:.0f} us",
+             f"store.verify() of {m['verify']['layers']} Llama-3-8B blocks ({m['verify']['tensors']} tensors, {m['verify']['bytes']} B): {m['verify']['verify_wall_ms']:.3f} ms wall, read-back included; "
+             f"plan.run of the same blocks: {m['verify']['plan_run_all_blocks_ms']:.3f} ms of device time"]
+    open(out + ".txt", "w").write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+    return 0
+
+
 def main_delta(args):
     results = {}
     for leg, limit in DELTA_LEG_SECONDS.items():
@@ -434,6 +548,7 @@ def main():
     ap.add_argument("--leg", default=None)
     ap.add_argument("--index", action="store_true", help="the sync index legs (i, j) instead of a-e")
     ap.add_argument("--delta", action="store_true", help="the variant store leg (k) instead of a-e")
+    ap.add_argument("--digest", action="store_true", help="the content digest leg (m) instead of a-e")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resident_decode"))
     args = ap.parse_args()
     if args.leg:                                          # a child: one leg, its result as one JSON line
@@ -443,6 +558,8 @@ def main():
         return main_index(args)
     if args.delta:
         return main_delta(args)
+    if args.digest:
+        return main_digest(args)
     results = {}
     for leg, limit in LEG_SECONDS.items():
         p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--layers", str(args.layers), "--reps", str(args.reps)],

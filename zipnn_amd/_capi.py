@@ -65,6 +65,11 @@ class ZnCBatchItem(ctypes.Structure):
                 ("d_delta", ctypes.c_void_p)]
 
 
+class ZnDigestItem(ctypes.Structure):
+    """struct zn_digest_item of include/zipnn_hip.h"""
+    _fields_ = [("d_src", ctypes.c_void_p), ("n", ctypes.c_size_t)]
+
+
 class ZnLib:
     """A loaded libzipnn_hip.so."""
 
@@ -149,6 +154,10 @@ class ZnLib:
         L.zn_plan_run.argtypes = [vp, vp, ci]
         L.zn_plan_destroy.restype = ci
         L.zn_plan_destroy.argtypes = [vp]
+        L.zn_digest_batch_dev.restype = ci
+        L.zn_digest_batch_dev.argtypes = [ctypes.POINTER(ZnDigestItem), sz, vp, vp]
+        L.zn_digest_host.restype = ci
+        L.zn_digest_host.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_ulonglong)]
         L.zn_copy_to_device.restype = ci; L.zn_copy_to_device.argtypes = [vp, vp, sz]
         L.zn_copy_to_host.restype = ci; L.zn_copy_to_host.argtypes = [vp, vp, sz]
         L.zn_release_workspace.restype = ci
@@ -470,6 +479,25 @@ class ZnLib:
 
     def plan_destroy(self, plan):
         self._check(self._L.zn_plan_destroy(plan))
+
+    # -- content digests ("zn64-1", include/zipnn_hip.h) --
+    def digest_batch_dev(self, items, out_ptr, stream=0):
+        """zn_digest_batch_dev.  items: iterable of (src_ptr, n): byte ranges in device memory -> their digests in the len(items) 8-byte slots at out_ptr
+        (device memory), one launch on `stream`, no host wait."""
+        items = list(items)
+        arr = (ZnDigestItem * max(len(items), 1))()
+        for i, (sp, n) in enumerate(items):
+            arr[i].d_src = sp or None
+            arr[i].n = n
+        self._check(self._L.zn_digest_batch_dev(arr, len(items), out_ptr or None, ctypes.c_void_p(stream or None)))
+
+    def digest_host(self, buf):
+        """zn_digest_host: the digest of a bytes-like object's bytes, on the host."""
+        mv = memoryview(buf).cast("B")
+        cb = _as_c_buffer(mv)
+        out = ctypes.c_ulonglong(0)
+        self._check(self._L.zn_digest_host(cb.addr, mv.nbytes, ctypes.byref(out)))
+        return int(out.value)
 
     def decode_status(self, stream=0):
         """zn_decode_status: wait for `stream`, raise what the last check=False decode call on this device would have raised."""

@@ -247,3 +247,75 @@ def build_decode_hints(lib, items):
         lib.hint_build_dev(it, h.data_ptr(), n)
         out.append(h[:n])
     return out
+
+
+# ---- content digests ("zn64-1": include/zipnn_hip.h) -------------------------------------------------------------------------
+DIGEST_ALGO = "zn64-1"
+
+
+class DigestMismatch(ValueError):
+    """Decoded or live bytes do not have the digest that was recorded for them.  `names`: the tensors concerned."""
+
+    def __init__(self, names, what="digest mismatch"):
+        self.names = list(names)
+        super().__init__(f"{what}: {', '.join(repr(n) for n in self.names)}")
+
+
+def digest_device_batch(lib, flats, stream=None, out=None):
+    """flats: contiguous uint8 tensors on ONE device (any byte address, any length) -> an int64 tensor on that device with their digests' bit patterns, by
+    one zn_digest_batch_dev launch on `stream` (a raw handle; default: the device's current stream).  Nothing waits: read the result behind the stream
+    (digests_to_ints), and keep `flats` alive until then.  out: len(flats) contiguous int64 slots on the device to write to instead of a new tensor."""
+    flats = list(flats)
+    dev = flats[0].device if flats else (out.device if out is not None else torch.device("cpu"))
+    if out is None:
+        out = torch.empty(max(len(flats), 1), dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or out.device != dev or not out.is_contiguous() or out.numel() < len(flats):
+        raise ValueError("digest: out must be a contiguous int64 tensor on the tensors' device, one slot per tensor")
+    if flats:
+        if any(f.dtype != torch.uint8 or f.device != dev or not f.is_contiguous() for f in flats):
+            raise ValueError("digest: contiguous uint8 tensors on one device")
+        with torch.cuda.device(dev) if dev.type == "cuda" else _nullctx():
+            lib.digest_batch_dev([(f.data_ptr() if f.numel() else 0, f.numel()) for f in flats], out.data_ptr(),
+                                 stream if stream is not None else _stream_handle(out))
+    return out[:len(flats)]
+
+
+def digests_to_ints(out):
+    """The one read-back of a digest_device_batch result (8 bytes per item; waits for the stream) -> list of unsigned ints."""
+    return [v & 0xFFFFFFFFFFFFFFFF for v in out.tolist()]
+
+
+def _host_bytes(x):
+    """A CPU tensor, numpy array or bytes-like -> a bytes-like object of its contiguous bytes."""
+    if isinstance(x, torch.Tensor):
+        return memoryview(flat_bytes(x.detach()).numpy())
+    import numpy as np
+    if isinstance(x, np.ndarray):
+        return memoryview(np.ascontiguousarray(x).reshape(-1).view(np.uint8))
+    return memoryview(x).cast("B")
+
+
+def digest_many(tensors):
+    """Digests of many tensors -> list of ints, in order.  Device tensors: ONE launch (per device) for all of them and one read-back of 8 bytes each;
+    CPU tensors, numpy arrays and bytes-like objects go through the host function (zn_digest_host).  The digest covers the contiguous bytes of each
+    (a non-contiguous tensor is made contiguous first).  An error-detecting code, not a cryptographic hash."""
+    from . import _capi
+    lib = _capi.lib()
+    tensors = list(tensors)
+    res = [None] * len(tensors)
+    by_dev = {}
+    for i, x in enumerate(tensors):
+        if isinstance(x, torch.Tensor) and x.is_cuda:
+            by_dev.setdefault(x.device, []).append((i, flat_bytes(x.detach())))
+        else:
+            res[i] = lib.digest_host(_host_bytes(x))
+    pending = [(items, digest_device_batch(lib, [f for _, f in items])) for items in by_dev.values()]
+    for items, out in pending:
+        for (i, _), v in zip(items, digests_to_ints(out)):
+            res[i] = v
+    return res
+
+
+def digest(x):
+    """The "zn64-1" content digest of a device tensor, a CPU tensor, a numpy array or a bytes-like object: an int below 2^64 (see digest_many)."""
+    return digest_many([x])[0]

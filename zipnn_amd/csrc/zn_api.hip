@@ -814,6 +814,57 @@ int zn_decompress_window_batch_dev(const zn_window_item* items, size_t count, vo
   } catch (...) { return ZN_E_ALLOC; }
 }
 
+// ---- content digests (zn_digest.hip) ----
+int zn_digest_host(const void* src, size_t n, unsigned long long* out) {
+  if (!out || (n && !src)) return ZN_E_ARG;
+  *out = (unsigned long long)zn_digest_scalar((const uint8_t*)src, n);
+  return ZN_OK;
+}
+
+int zn_digest_batch_dev(const zn_digest_item* items, size_t count, unsigned long long* d_out, void* stream_) {
+  try {
+    if (count == 0) return ZN_OK;
+    if (!items || !d_out || (((uintptr_t)d_out) & 7u) != 0 || count > 0x7FFFFFFFull) return ZN_E_ARG;
+    std::vector<ZnDigSeg> segs(count);
+    uint64_t wg = 0;
+    for (size_t i = 0; i < count; i++) {
+      if (items[i].n && !items[i].d_src) return ZN_E_ARG;
+      if ((uint64_t)items[i].n > (0x7FFFFFFFull << 18)) return ZN_E_ARG;      // (more blocks than a grid has workgroups; also keeps the rounding below from wrapping)
+      segs[i].src = (const uint8_t*)items[i].d_src; segs[i].n = items[i].n; segs[i].wg0 = (uint32_t)wg; segs[i].slot = (uint32_t)i;
+      wg += ((uint64_t)items[i].n + 262143u) >> 18;              // one workgroup per 256 KiB block
+      if (wg > 0x7FFFFFFFull) return ZN_E_ARG;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    t_kernels.clear();
+    if (count == 1) {                              // (the item travels as a kernel argument: no table, no workspace, nothing to wait for)
+      zn_launch_digest(segs[0], nullptr, 1, (uint32_t)wg, d_out, stream);
+      const hipError_t el = hipGetLastError();
+      if (el != hipSuccess) { t_hip_err = std::string("kernel launch: ") + hipGetErrorString(el); return ZN_E_HIP; }
+      return ZN_OK;
+    }
+    int dev = 0;
+    ZN_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64) return ZN_E_ARG;
+    std::lock_guard<std::mutex> lk(g_dev_mu[dev]);
+    Workspace& w = g_ws[dev];
+    int rc;
+    const size_t seg_units = (count * sizeof(ZnDigSeg) + sizeof(ZnSeg) - 1u) / sizeof(ZnSeg);      // (the batched calls' staging, which is kept in ZnSeg units)
+    if ((rc = ws_reserve(w, WS_SEGS, seg_units * sizeof(ZnSeg)))) return rc;
+    if ((rc = ws_acquire(w, stream))) return rc;
+    ZN_HIP(hipEventSynchronize(w.busy));           // the previous batched call may still be reading the pinned staging
+    if (w.h_segs_cap < seg_units) {
+      if (w.h_segs) { ZN_HIP(hipHostFree(w.h_segs)); w.h_segs = nullptr; w.h_segs_cap = 0; }
+      ZN_HIP(hipHostMalloc((void**)&w.h_segs, seg_units * sizeof(ZnSeg), hipHostMallocDefault));
+      w.h_segs_cap = seg_units;
+    }
+    memcpy(w.h_segs, segs.data(), count * sizeof(ZnDigSeg));
+    ZN_HIP(hipMemcpyAsync(w.buf[WS_SEGS], w.h_segs, count * sizeof(ZnDigSeg), hipMemcpyHostToDevice, stream));
+    zn_launch_digest(segs[0], (const ZnDigSeg*)w.buf[WS_SEGS], (uint32_t)count, (uint32_t)wg, d_out, stream);
+    { const hipError_t el = hipGetLastError(); if (el != hipSuccess) { t_hip_err = std::string("kernel launch: ") + hipGetErrorString(el); (void)ws_release(w, stream, true); return ZN_E_HIP; } }
+    return ws_release(w, stream, true);
+  } catch (...) { return ZN_E_ALLOC; }
+}
+
 }  // extern "C"
 // A prepared batched decode: everything build_segments works out, and the segment table in device memory of its own — zn_release_workspace frees none of it,
 // and a run stages nothing: no host-to-device copy, no wait for the pinned staging buffer that one-shot batched calls share.

@@ -131,6 +131,14 @@ void zn_launch_encode_onepass(int P, const ZnESeg& one, const ZnESeg* d_segs, ui
                               uint64_t* d_lb, uint32_t* d_ticket, uint32_t* d_status, uint32_t gen, bool delta, hipStream_t stream);
 void zn_scan_geometry(uint64_t PK, uint64_t* T, uint32_t* blocks);     // entries per block / number of blocks for PK entries
 
+// ---- content digests ("zn64-1") : zn_digest.hip ----
+// One item of a digest launch: n bytes at src (any byte address), its first workgroup — one per 256 KiB block, none for an empty item — and its slot of d_out.
+// A single item travels as a kernel argument, a batch as a table in device memory (every item of the call, in order: slot i is item i).
+struct ZnDigSeg { const uint8_t* src; uint64_t n; uint32_t wg0; uint32_t slot; };
+// d_out[slot] = the digest, by two launches on `stream` (the slots' initial values, then one 64-bit atomic add per block); total_wg = Σ blocks
+void zn_launch_digest(const ZnDigSeg& one, const ZnDigSeg* d_segs, uint32_t nseg, uint32_t total_wg, unsigned long long* d_out, hipStream_t stream);
+uint64_t zn_digest_scalar(const uint8_t* b, size_t n);      // the same value on the host
+
 // kernel-name log for zn_last_kernels()
 void zn_note_kernel(const char* name);
 

@@ -114,6 +114,14 @@ class ResidentCheckpoint:
         ft.apply_(model)          # tensors that hold the base's values now hold the fine-tune's, in place (XOR is its own inverse) …
         ft.revert_(model)         # … and the base's again
         ft.info(n)["delta"]       # True, False or "same"
+
+    CONTENT DIGESTS ("zn64-1"; an error-detecting code, not a cryptographic hash) let a store answer whether what it decodes is still what it was built from:
+
+        store = ResidentCheckpoint.from_state_dict(sd, "cuda:0", digests=True)       # or from_file(path, dev, digests=True, verify=True)
+        store.digests(); store.info(n)["digest"]                                     # ints below 2^64
+        store.verify()            # every tensor decoded into one scratch buffer and digested on the device -> {name: bool}, or DigestMismatch
+        store.holds(model)        # do the live tensors hold this store's values?
+        ft.apply_(model, guard=True); ft.revert_(model, guard=True)                  # raise before touching anything if they hold the wrong values
     """
 
     def __init__(self, device, entries, held_bytes, keep=()):
@@ -123,6 +131,7 @@ class ResidentCheckpoint:
         self._keep = tuple(keep)              # the allocations the entries are views of
         self._index = None                     # the allocation the entries' hints are views of (build_index)
         self._index_bytes = 0
+        self._digests = None                   # {name: "zn64-1" digest of the tensor's bytes} when the store was built with digests, else None
 
     # ---- constructors -------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -137,11 +146,19 @@ class ResidentCheckpoint:
         return dev
 
     @classmethod
-    def from_file(cls, path, device="cuda:0", index=False):
+    def from_file(cls, path, device="cuda:0", index=False, digests=False, verify=False):
         """A `.znn.safetensors` file (this library's or the reference's): its data section goes to `device` once, in one transfer, and stays.
-        index=True: build_index() on the new store."""
+        index=True: build_index() on the new store.
+        digests=True: the store records a content digest per tensor (digests(), verify(), holds()).  A file written with digests
+        (compress_safetensors_file(..., digests=True)) brings them, and they are taken from it — they describe what the WRITER compressed.  A file
+        without them is decoded once and the store records what it got: that only pins the state at load — damage that happened before is not seen.
+        verify=True: the file's digests are checked against one decode of every tensor at load; DigestMismatch names the tensors that differ, and a file
+        without digests is an error, not a pass."""
         from . import safetensors_io
         dev = cls._work_device(device)
+        recorded = safetensors_io.file_digests(safetensors_io.read_metadata(path)) if (digests or verify) else None
+        if verify and recorded is None:
+            raise ValueError(f"{path}: the file carries no digests (znn_digests): nothing to verify against")
         up = safetensors_io._upload_file(path, dev)
         if up is None:
             raise ValueError(f"{path}: the container names a dtype this loader does not know")
@@ -168,6 +185,15 @@ class ResidentCheckpoint:
         store = cls(dev, entries, blob.numel() + extra, keep=(blob,))
         if index:
             store.build_index()
+        if recorded is not None:
+            missing = [n for n in store.keys() if n not in recorded]
+            if missing:
+                raise ValueError(f"{path}: znn_digests lacks {missing[:3]}{' …' if len(missing) > 3 else ''}")
+            store._digests = {n: recorded[n] for n in store.keys()}
+            if verify:
+                store.verify()
+        elif digests:
+            store._digests = store._decoded_digests(store.keys())
         return store
 
     @staticmethod
@@ -196,10 +222,12 @@ class ResidentCheckpoint:
     _BUILD_GROUP_BYTES = 1 << 30
 
     @classmethod
-    def from_state_dict(cls, sd, device="cuda:0", threshold=0.95, method=None, index=False, base=None):
+    def from_state_dict(cls, sd, device="cuda:0", threshold=0.95, method=None, index=False, base=None, digests=False):
         """Compress the tensors of a state dict on `device` (one batched call) and keep the bodies, trimmed to their lengths and packed at
         256-byte boundaries of one allocation.  A tensor whose body would not be smaller than the tensor itself — and every tensor the codec
         does not take: integers, float64, empty ones — is kept as it is.  index=True: build_index() on the new store.
+        digests=True: the SOURCE tensors are digested on the device, all of them in one batched launch, before anything is compressed: the store then knows
+        what it was built from (digests(), verify(), holds(), the guards of apply_ / revert_).
 
         base: the store becomes a VARIANT of it — another ResidentCheckpoint on the same device (compressed or not, a variant itself), a mapping of
         names to tensors on the device, or a module (its named parameters and buffers).  A tensor the base has under the same name with the same dtype,
@@ -245,6 +273,13 @@ class ResidentCheckpoint:
         def trimmed(bodies):                   # (out of the compress arena, which is as large as the tensors themselves)
             return [b.clone() for b in bodies]
 
+        recorded = None
+        if digests:                            # (the sources, before compression; raw entries are digested too)
+            src = {name: t for name, t, _ in todo}
+            src.update({name: e.raw for name, e in entries.items()})
+            order = list(sd.keys())
+            with _device_of(dev):
+                recorded = dict(zip(order, codec.digests_to_ints(codec.digest_device_batch(lib, [codec.flat_bytes(src[n]) for n in order]))))
         keep, held = [], 0
         if todo:
             with _device_of(dev):
@@ -314,6 +349,7 @@ class ResidentCheckpoint:
         if base is not None:
             keep.append(base)
         store = cls(dev, [entries[name] for name in sd.keys()], held, keep=keep)
+        store._digests = recorded
         if index:
             store.build_index()
         return store
@@ -443,7 +479,8 @@ class ResidentCheckpoint:
         e = self._entries[name]
         return {"shape": list(e.shape), "dtype": e.dtype, "nbytes": e.nbytes, "compressed": e.compressed, "delta": e.delta,
                 "resident_bytes": e.body.numel() if e.compressed else (0 if e.delta == "same" else e.nbytes),
-                "index_bytes": e.hints.numel() if e.hints is not None else 0}
+                "index_bytes": e.hints.numel() if e.hints is not None else 0,
+                "digest": self._digests[name] if self._digests is not None else None}
 
     @property
     def nbytes(self):
@@ -523,6 +560,110 @@ class ResidentCheckpoint:
         with _device_of(self.device):
             _capi.lib().decode_status(_stream_of(self.device, stream))
 
+    # ---- content digests ("zn64-1") ------------------------------------------------------------------------------
+    @property
+    def has_digests(self):
+        return self._digests is not None
+
+    def _need_digests(self):
+        if self._digests is None:
+            raise ValueError("the store has no digests: build it with digests=True")
+
+    def digests(self):
+        """{name: digest} of the tensors' bytes as the store recorded them (from_state_dict / from_file with digests=True): ints below 2^64.  An
+        error-detecting code, not a cryptographic hash."""
+        self._need_digests()
+        return dict(self._digests)
+
+    def _decoded_digests(self, names):
+        """-> {name: digest of what the store decodes for it NOW}: every tensor through the store's normal path — hinted if indexed, base followed by an in-place
+        delta for a variant — into ONE scratch buffer sized for the largest tensor (never a second copy of the model), as many tensors per group as fit;
+        each group's tensors digested by one zn_digest_batch_dev call behind its decode on the current stream (the stream orders the buffer's reuse); tensors the
+        store holds plainly are digested where they lie; one read-back at the end.  The decodes are unchecked: the digest is the verdict."""
+        lib = _capi.lib()
+        names = list(dict.fromkeys(names))
+        ents = [self._entries[n] for n in names]
+        plain = [e for e in ents if not (e.decoded and e.nbytes)]
+        todo = [e for e in ents if e.decoded and e.nbytes]
+        out = torch.empty(max(len(names), 1), dtype=torch.int64, device=self.device)      # slot order: the plain tensors, then the decoded ones group by group
+        with _device_of(self.device):
+            stream = _stream_of(self.device)
+            if plain:
+                nothing = torch.empty(0, dtype=torch.uint8, device=self.device)
+                codec.digest_device_batch(lib, [codec.flat_bytes(e.raw) if e.raw is not None else nothing for e in plain], stream, out=out[:len(plain)])
+            if todo:
+                scratch = torch.empty(max(_round_up(e.nbytes) for e in todo), dtype=torch.uint8, device=self.device)
+                groups, cur, o = [], [], 0
+                for e in todo:
+                    if cur and o + _round_up(e.nbytes) > scratch.numel():
+                        groups.append(cur)
+                        cur, o = [], 0
+                    cur.append((e, scratch[o:o + e.nbytes]))
+                    o += _round_up(e.nbytes)
+                groups.append(cur)
+                k = len(plain)
+                for grp in groups:
+                    self._decode([(e, 0, e.chunks, flat) for e, flat in grp], False)
+                    codec.digest_device_batch(lib, [flat for _, flat in grp], stream, out=out[k:k + len(grp)])
+                    k += len(grp)
+            vals = codec.digests_to_ints(out[:len(names)])
+        return dict(zip([e.name for e in plain + todo], vals))
+
+    def verify(self, names=None, raise_=True):
+        """Is what the store decodes still what it was built from?  Decodes every named tensor (default: all) through the store's normal path into a scratch
+        buffer sized for the largest one, digests the decoded bytes on the device and compares with the recorded digests (_decoded_digests: one digest launch
+        per group, one read-back).  -> {name: bool}; raise_=True: DigestMismatch (a ValueError) naming the tensors that differ."""
+        self._need_digests()
+        names = self.keys() if names is None else list(names)
+        got = self._decoded_digests(names)
+        res = {n: got[n] == self._digests[n] for n in names}
+        bad = [n for n in names if not res[n]]
+        if bad and raise_:
+            raise codec.DigestMismatch(bad, "the store no longer decodes what it was built from")
+        return res
+
+    def _live_digests(self, pairs):
+        """[(key, tensor)] -> {key: digest of the live tensor's bytes}: one batched launch, one read-back."""
+        if not pairs:
+            return {}
+        with _device_of(self.device):
+            vals = codec.digests_to_ints(codec.digest_device_batch(_capi.lib(), [codec.flat_bytes(t) for _, t in pairs], _stream_of(self.device)))
+        return {k: v for (k, _), v in zip(pairs, vals)}
+
+    def holds(self, target):
+        """Do live tensors hold this store's values?  target: a module (named parameters and buffers) or a mapping of names to contiguous tensors on the
+        store's device.  -> {name: bool} for the names the store has: the live tensors digested where they lie (one launch), compared with the recorded digests."""
+        self._need_digests()
+        tg = self._targets(target)
+        live = self._live_digests([(e.name, t) for e, t in tg])
+        return {e.name: live[e.name] == self._digests[e.name] for e, _ in tg}
+
+    def _guard(self, target, want_base):
+        """apply_ / revert_ with guard=True: raise DigestMismatch unless the target's tensors hold the base's values (want_base) or this store's.  The base's
+        digests: a resident base's recorded ones; a base given as plain tensors has none recorded — what those tensors hold NOW is digested beside the target."""
+        self._need_digests()
+        tg = [(e, t) for e, t in self._targets(target) if e.nbytes]
+        pairs, want = [(("live", e.name), t) for e, t in tg], {}
+        for e, t in tg:
+            if not want_base:
+                want[e.name] = self._digests[e.name]
+            elif e.restore is None:
+                continue                           # (the base has no such tensor: apply_ overwrites whatever is there)
+            elif e.restore[0] == "tensor":
+                pairs.append((("base", e.name), e.restore[1]))
+            else:
+                bstore, be = e.restore[1], e.restore[2]
+                if bstore._digests is None:
+                    raise ValueError(f"guard: the base store has no digests (build it with digests=True) — {e.name}")
+                want[e.name] = bstore._digests[be.name]
+        got = self._live_digests(pairs)
+        for (kind, name), _ in pairs:
+            if kind == "base":
+                want[name] = got[(kind, name)]
+        bad = [e.name for e, _ in tg if e.name in want and got[("live", e.name)] != want[e.name]]
+        if bad:
+            raise codec.DigestMismatch(bad, "guard: the tensors do not hold the " + ("base's" if want_base else "variant's") + " values")
+
     # ---- a variant applied to live weights ------------------------------------------------------------------------------------
     def _targets(self, target):
         """target: a module (named parameters and buffers) or a mapping -> [(entry, tensor)] for the names the store has."""
@@ -542,12 +683,15 @@ class ResidentCheckpoint:
             out.append((e, t))
         return out
 
-    def apply_(self, target, check=True):
+    def apply_(self, target, check=True, guard=False):
         """Turn live BASE weights into the fine-tune's, in place: `target` is a module or a mapping of names to contiguous tensors on the store's device that
         hold the base's values.  Delta entries are XORed over them by an in-place decode (d_dst == d_delta, include/zipnn_hip.h) — no second copy of the
         weights, no read of the base —, plain entries are overwritten, "same" entries are left alone; one batched launch set on the current stream.
-        Nothing is tracked: applying twice (or to tensors that do not hold the base) XORs the delta in twice and is the caller's mistake.  If `target` is
+        Nothing is tracked: applying twice (or to tensors that do not hold the base) XORs the delta in twice and is the caller's mistake — unless guard=True
+        (a store with digests): the live tensors are digested first and must hold the BASE's values, else DigestMismatch is raised before anything is touched.  If `target` is
         the very tensors this store holds as its plain base, the store decodes wrong values until revert_.  -> the names changed."""
+        if guard:
+            self._guard(target, True)
         work, inplace, done = [], [], []
         for e, t in self._targets(target):
             if e.delta == "same" or not e.nbytes:
@@ -565,10 +709,13 @@ class ResidentCheckpoint:
         self._run_sets(sets, check)
         return done
 
-    def revert_(self, target, check=True):
+    def revert_(self, target, check=True, guard=False):
         """The inverse of apply_: delta entries by the same in-place call again (XOR is its own inverse), plain entries restored from the base — its
         tensor copied, or its resident body decoded — where the base has the tensor with the same dtype and shape.  -> the names that could NOT be
-        reverted (plain entries with nothing to restore from: they stay as they are).  Reverting what was not applied is the caller's mistake."""
+        reverted (plain entries with nothing to restore from: they stay as they are).  Reverting what was not applied is the caller's mistake — unless
+        guard=True (a store with digests): the live tensors must hold THIS store's values, else DigestMismatch is raised before anything is touched."""
+        if guard:
+            self._guard(target, False)
         work, inplace, stay, via = [], [], [], {}
         for e, t in self._targets(target):
             if e.delta == "same" or not e.nbytes:

@@ -13,25 +13,83 @@ from .zipnn import (COMPRESSED_DTYPE, COMPRESSION_METHOD, METADATA_KEY, ZipNN, b
                     get_compressed_tensors_metadata, set_compressed_tensors_metadata)
 
 SUFFIX = ".znn.safetensors"
+_DIGEST_GROUP_BYTES = 256 << 20      # compress_safetensors_file(digests=True), per-tensor path: tensors are digested as they are read, in groups of at most this many bytes
+DIGESTS_KEY = "znn_digests"          # file metadata: a JSON string {"algo": "zn64-1", "tensors": {name: 16 hex digits}} — digests of the DECODED bytes of every tensor
 
 
-def compress_safetensors_file(filename, out_path=None, device="cpu", method=None, batched=None):
+def read_metadata(filename):
+    """The `__metadata__` dict of a safetensors container ({} when it has none)."""
+    import json
+    with open(filename, "rb") as f:
+        n = int.from_bytes(f.read(8), "little")
+        return dict(json.loads(f.read(n)).get("__metadata__") or {})
+
+
+def file_digests(metadata):
+    """-> {name: digest} from a file's metadata, or None when it carries none.  An algorithm this library does not know is an error."""
+    import json
+    from . import codec
+    raw = metadata.get(DIGESTS_KEY)
+    if raw is None:
+        return None
+    d = json.loads(raw)
+    if d.get("algo") != codec.DIGEST_ALGO:
+        raise ValueError(f"{DIGESTS_KEY}: unknown digest algorithm {d.get('algo')!r} (this library knows {codec.DIGEST_ALGO!r})")
+    return {name: int(h, 16) for name, h in d["tensors"].items()}
+
+
+def _set_digests_metadata(metadata, names, values):
+    import json
+    from . import codec
+    metadata[DIGESTS_KEY] = json.dumps({"algo": codec.DIGEST_ALGO, "tensors": {n: f"{v:016x}" for n, v in zip(names, values)}})
+
+
+def check_digests(tensors, want, what):
+    """tensors: {name: tensor} as decoded; want: {name: digest}.  Device tensors: one batched launch; CPU tensors: the host function.  Raises DigestMismatch."""
+    from . import codec
+    names = list(tensors.keys())
+    missing = [n for n in names if n not in want]
+    if missing:
+        raise ValueError(f"{what}: {DIGESTS_KEY} lacks {missing[:3]}{' …' if len(missing) > 3 else ''}")
+    got = codec.digest_many([tensors[n] for n in names])
+    bad = [n for n, g in zip(names, got) if g != want[n]]
+    if bad:
+        raise codec.DigestMismatch(bad, f"{what}: decoded bytes differ from the file's digests")
+
+
+def compress_safetensors_file(filename, out_path=None, device="cpu", method=None, batched=None, digests=False):
     """-> path of the compressed file.  `device` = where tensors are staged for compression
     ("cuda:N" compresses in HBM; the compressed frames come back to the host for writing).  Tensors staged in HBM
-    are compressed by ONE batched call for the whole file (`batched=None`: automatic; True forces it)."""
+    are compressed by ONE batched call for the whole file (`batched=None`: automatic; True forces it).
+    digests=True: the metadata also gets `znn_digests`, the content digest ("zn64-1") of every tensor's bytes, compressed or not, taken from the SOURCE
+    tensors (on the device path in one launch over the uploaded data section; on the per-tensor path as they are read, a group of at most 256 MiB — or one larger
+    tensor — at a time, which is all the option holds beyond the compression's own memory): load_file(..., verify=True) and ResidentCheckpoint.from_file check decodes against
+    it.  Readers that do not know the key ignore it; with the default the file is byte for byte what it was without this option."""
     from safetensors import safe_open
     from safetensors.torch import save_file
     assert filename.endswith(".safetensors")
     out_path = out_path or filename[: -len(".safetensors")] + SUFFIX
     if torch.device(device).type == "cuda" and batched is not False:
-        done = _compress_file_on_device(filename, out_path, torch.device(device), method)
+        done = _compress_file_on_device(filename, out_path, torch.device(device), method, digests)
         if done is not None:
             return done
     tensors, infos = {}, {}
     batch = []                                        # (name, tensor, header, planes, bits, bytes, chunk)
+    recorded, pending, pending_bytes = {}, [], 0      # digests=True: the tensors as read are digested in groups of at most _DIGEST_GROUP_BYTES (or one larger tensor) …
+
+    def digest_pending():
+        from . import codec
+        recorded.update(zip([n for n, _ in pending], codec.digest_many([t for _, t in pending])))
+        pending.clear()
     with safe_open(filename, "pt", device) as f:
         for name in f.keys():
             t = f.get_tensor(name)
+            if digests:                               # (… so that no more than a group is held beyond what the compression itself keeps)
+                if pending and pending_bytes + t.numel() * t.element_size() > _DIGEST_GROUP_BYTES:
+                    digest_pending()
+                    pending_bytes = 0
+                pending.append((name, t))
+                pending_bytes += t.numel() * t.element_size()
             if not torch.is_floating_point(t) or t.dtype == torch.float64 or t.numel() == 0:
                 tensors[name] = t.cpu()
                 continue
@@ -46,6 +104,8 @@ def compress_safetensors_file(filename, out_path=None, device="cpu", method=None
             tensors[name] = torch.frombuffer(bytearray(frame), dtype=COMPRESSED_DTYPE)
             infos[name] = build_compressed_tensor_info(t)
         metadata = dict(f.metadata() or {})
+        if pending:
+            digest_pending()
     if batch:
         # tensors staged in HBM: one batched compress for the whole file (zn_compress_batch_dev)
         from . import _capi, codec
@@ -64,11 +124,13 @@ def compress_safetensors_file(filename, out_path=None, device="cpu", method=None
     if not metadata:
         metadata = {"format": "pt"}                       # the reference silently drops the list when a file has no metadata
     set_compressed_tensors_metadata(infos, metadata)
+    if digests:
+        _set_digests_metadata(metadata, list(recorded.keys()), list(recorded.values()))
     save_file(tensors, out_path, metadata)
     return out_path
 
 
-def _compress_file_on_device(filename, out_path, dev, method):
+def _compress_file_on_device(filename, out_path, dev, method, digests=False):
     """compress_safetensors_file with the tensors staged in HBM, the way decode_file_on_device loads: the file's data section crosses PCIe ONCE
     (pinned multi-threaded upload of the mapping), ONE batched compress writes every body into one arena — each behind a 256-byte gap —, the
     arena comes back in ONE transfer and the frame headers are written into the gaps on the host: the frames handed to safetensors are views of that one
@@ -142,6 +204,10 @@ def _compress_file_on_device(filename, out_path, dev, method):
     if not metadata:
         metadata = {"format": "pt"}                                                # the reference silently drops the list when a file has no metadata
     set_compressed_tensors_metadata(infos, metadata)
+    if digests:
+        # every tensor where the upload put it (safetensors aligns nothing: the kernel takes any byte address), one launch for the file
+        flats = [blob[layout[name][2]:layout[name][3]] for name in order]
+        _set_digests_metadata(metadata, order, codec.digests_to_ints(codec.digest_device_batch(lib, flats)) if flats else [])
     save_file({name: tensors[name] for name in order}, out_path, metadata)
     return out_path
 
@@ -347,16 +413,26 @@ def _decode_uploaded(lib, codec, dev, layout, infos, plan, total, blob, use_aren
     return out
 
 
-def load_file(filename, device="cuda:0", timings=None):
+def load_file(filename, device="cuda:0", timings=None, verify=False):
     """Load a (possibly ZipNN-compressed) safetensors file straight onto `device` -> {name: tensor}: one transfer of the file's data
     section, one batched decode (decode_file_on_device).  The batched counterpart of looping SafeOpen.get_tensor (reference
     zipnn.py:1592-1626, scripts/zipnn_decompress_safetensors.py:75-120) — and what SafeOpen itself uses behind get_tensor for a
     device target.  timings: an optional dict that receives the seconds spent mapping the file and parsing every header (`read_s`),
-    moving the data section to the device (`h2d_s`) and decoding (`decode_s`), each ended by a device sync."""
+    moving the data section to the device (`h2d_s`) and decoding (`decode_s`), each ended by a device sync.
+    verify=True: the decoded tensors are digested — on a GPU all of them by one batched launch, with device="cpu" by the host function — and compared with
+    the file's `znn_digests` (compress_safetensors_file(..., digests=True)); DigestMismatch names the tensors that differ.  A file without digests is an
+    error then, not a pass."""
     dev = torch.device(device)
+    want = None
+    if verify:
+        want = file_digests(read_metadata(filename))
+        if want is None:
+            raise ValueError(f"{filename}: the file carries no digests ({DIGESTS_KEY}): nothing to verify against")
     out = decode_file_on_device(filename, dev, timings=timings)
     if out is None:
-        return _load_file_per_tensor(filename, dev, timings)
+        out = _load_file_per_tensor(filename, dev, timings)
+    if want is not None:
+        check_digests(out, want, filename)
     # (file order, as safetensors' own load_file returns it)
     return out
 
