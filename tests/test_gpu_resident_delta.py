@@ -41,9 +41,10 @@ def test_in_place_delta_decode_every_entry_point_on_the_device(lib, dev, case, o
 
 
 @pytest.mark.parametrize("off", (0, 4), ids=lambda o: f"mod16={o}")
-@pytest.mark.parametrize("name", ["identical", "unrelated", "skew", "skew4", "tl12-2", "tl12-4"])
+@pytest.mark.parametrize("name", ["identical", "unrelated", "skew", "skew4", "u11", "burst16", "tl12-2", "tl12-4"])
 def test_in_place_with_rle_raw_hostile_and_table_log_12_planes_on_the_device(lib, dev, name, off):
-    """Every plane RLE zero, raw planes, every plane Huffman-coded with 1-bit codes (the fused kernel's further passes over its own output), and a
+    """Every plane RLE zero, raw planes, every plane Huffman-coded with 1-bit codes (the fused kernel's further passes over its own output), 11-bit codes,
+    tiles denser than the stream average in chunks of 2 * C (burst16), and a
     tableLog-12 plane behind planes the fused kernel has already XORed into the base (it hands the base back and leaves the chunk to the generic path)."""
     case, a, b, body = U.tl12_case(int(name[-1])) if name.startswith("tl12") else U.more_case(name)
     U.check_entry_points(lib, case, a, b, body, off, dev)
