@@ -25,6 +25,12 @@ step, so that low mantissa bits change everywhere:
      tensor in the same process (decode digest decode digest: the decode's two runs are the A/A spread, and the decode is the yardstick — a verify that costs
      more than the decode it follows is not worth having); a ragged batch of 291 tensors (the Llama-3-8B tensor list at a quarter of its widths, packed back
      to back at whatever byte address they fall on) in one launch; store.verify() on the four-block store of leg b
+--delta-file: delta checkpoint files instead (ResidentCheckpoint.save_file / from_file(base=)), into profiles/resident_delta_file.{json,txt}: the
+blocks of leg b as the base, the two fine-tunes of --delta:
+  n  per fine-tune: bytes of the delta file against the plain `.znn.safetensors` of the same tensors and the raw tensors; wall time of from_file(delta,
+     base=store) against from_state_dict(ft_sd, base=store) with ft_sd already on the device; from_file with verify_base over a base store with recorded
+     digests, over one without, and with verify_base=False; plan.run of one block from the built variant and from the loaded one, interleaved (A B A B: the
+     built variant's two runs are the A/A spread — the two run the same kernels on byte-equal bodies)
 """
 import argparse
 import json
@@ -40,6 +46,7 @@ LEG_SECONDS = {"a": 240, "b": 240, "c": 300, "d": 240, "e": 300}
 INDEX_LEG_SECONDS = {"i": 420, "j": 300}
 DELTA_LEG_SECONDS = {"k": 420}
 DIGEST_LEG_SECONDS = {"m": 420}
+DELTA_FILE_LEG_SECONDS = {"n": 420}
 CH = 256 * 1024
 
 
@@ -370,6 +377,62 @@ def leg_k(args):
     return res
 
 
+def leg_n(args):
+    import tempfile
+    import torch
+    from zipnn_amd import ResidentCheckpoint
+    sd, per = _blocks(args.layers)
+    names = per[0]
+    res = {"layers": args.layers, "block_bytes": sum(sd[k].numel() * 2 for k in names), "fine_tunes": []}
+
+    def timed(fn, reps=1):
+        ts, r = [], None
+        for _ in range(reps):
+            r = None
+            torch.cuda.synchronize(); t0 = time.perf_counter(); r = fn(); torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return r, statistics.median(ts)
+    base = ResidentCheckpoint.from_state_dict(sd, "cuda:0", index=True, digests=True)
+    bare = ResidentCheckpoint.from_state_dict(sd, "cuda:0", index=True)              # the same base without recorded digests
+    with tempfile.TemporaryDirectory() as tmp:
+        for kind in ("sparse", "drift"):
+            ft = _fine_tune(sd, kind, 21)
+            built, t_build = timed(lambda: ResidentCheckpoint.from_state_dict(ft, "cuda:0", base=base), 3)
+            d_path, t_save = timed(lambda: built.save_file(os.path.join(tmp, kind + ".delta.znn.safetensors")))
+            p_path = ResidentCheckpoint.from_state_dict(ft, "cuda:0").save_file(os.path.join(tmp, kind + ".plain.znn.safetensors"))
+            loaded, t_load = timed(lambda: ResidentCheckpoint.from_file(d_path, "cuda:0", base=base), 5)
+            _, t_load_bare = timed(lambda: ResidentCheckpoint.from_file(d_path, "cuda:0", base=bare), 5)
+            _, t_load_nocheck = timed(lambda: ResidentCheckpoint.from_file(d_path, "cuda:0", base=base, verify_base=False), 5)
+            for k in ft:
+                assert built.info(k)["delta"] == loaded.info(k)["delta"], (kind, k)
+                if built.info(k)["compressed"]:
+                    assert torch.equal(built._entries[k].body, loaded._entries[k].body), (kind, k)
+            r = {"kind": kind, "raw_bytes": built.nbytes, "delta_file_bytes": os.path.getsize(d_path), "plain_file_bytes": os.path.getsize(p_path),
+                 "delta_entries": sum(1 for k in ft if built.info(k)["delta"] is True), "tensors": len(ft),
+                 "built_resident_bytes": built.resident_bytes, "loaded_resident_bytes": loaded.resident_bytes,
+                 "wall_s": {"from_state_dict": t_build, "save_file": t_save, "from_file": t_load, "from_file_base_without_digests": t_load_bare,
+                            "from_file_verify_base_off": t_load_nocheck}}
+            scratch = torch.empty(built.scratch_bytes(names), dtype=torch.uint8, device="cuda")
+            runs, kernels = {"built": [], "loaded": []}, {}
+            for _ in range(2):                                    # A B A B
+                for leg, st in (("built", built), ("loaded", loaded)):
+                    plan = st.plan(names, into=scratch)
+                    t = _events_ms(plan.run, args.reps)
+                    plan.status()
+                    for k in names:
+                        assert _same(plan.tensors[k], ft[k]), (kind, leg, k)
+                    runs[leg].append(t["median_ms"])
+                    kernels[leg] = _capi_kernels()
+                    plan.close()
+            r["plan_run_ms"], r["kernels"] = runs, kernels
+            r["aa_spread"] = abs(runs["built"][0] - runs["built"][1]) / min(runs["built"])
+            r["loaded_vs_built"] = (sum(runs["loaded"]) / 2) / (sum(runs["built"]) / 2) - 1.0
+            res["fine_tunes"].append(r)
+            del built, loaded, ft, scratch
+            torch.cuda.empty_cache()
+    return res
+
+
 def leg_m(args):
     import torch
     import bench
@@ -510,6 +573,37 @@ def main_delta(args):
     return 0
 
 
+def main_delta_file(args):
+    results = {}
+    for leg, limit in DELTA_FILE_LEG_SECONDS.items():
+        p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--layers", str(args.layers), "--reps", str(args.reps)],
+                           capture_output=True, text=True)
+        line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+        if p.returncode != 0 or not line:
+            print(f"leg {leg} failed (exit {p.returncode}); nothing further is started\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}")
+            return 1
+        results[leg] = json.loads(line[0][7:])
+        print(f"leg {leg}: ok", flush=True)
+    out = args.out if args.out != os.path.join(ROOT, "profiles", "resident_decode") else os.path.join(ROOT, "profiles", "resident_delta_file")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    json.dump(results, open(out + ".json", "w"), indent=1)
+    n = results["n"]
+    lines = [f"delta file probe (ResidentCheckpoint.save_file / from_file(base=)): {n['layers']} Llama-3-8B blocks, bf16, over a resident base with an index; wall times are medians, "
+             "ended by a device sync; plan.run by device events, median ms; loaded bodies checked byte-equal to the built ones, every decode against its source"]
+    for r in n["fine_tunes"]:
+        w, q = r["wall_s"], r["plan_run_ms"]
+        lines.append(f"({r['kind']}) file bytes: delta {r['delta_file_bytes']} = {r['delta_file_bytes'] / r['raw_bytes']:.4f} of the raw tensors ({r['raw_bytes']} B), plain .znn.safetensors "
+                     f"{r['plain_file_bytes']} = {r['plain_file_bytes'] / r['raw_bytes']:.4f}; {r['delta_entries']} of {r['tensors']} tensors delta-coded; resident: built {r['built_resident_bytes']} B, loaded {r['loaded_resident_bytes']} B")
+        lines.append(f"    wall: from_file(delta, base=store) {w['from_file'] * 1e3:.1f} ms against from_state_dict(ft_sd, base=store) {w['from_state_dict'] * 1e3:.1f} ms (ft_sd on the device); save_file {w['save_file'] * 1e3:.1f} ms")
+        lines.append(f"    verify_base: base with recorded digests {w['from_file'] * 1e3:.1f} ms, base without (digested at load) {w['from_file_base_without_digests'] * 1e3:.1f} ms, verify_base=False {w['from_file_verify_base_off'] * 1e3:.1f} ms")
+        lines.append(f"    plan.run of one block ({n['block_bytes']} B): built variant {q['built'][0]:.4f} / {q['built'][1]:.4f} (A/A spread {100 * r['aa_spread']:.1f} %), loaded variant "
+                     f"{q['loaded'][0]:.4f} / {q['loaded'][1]:.4f} ({100 * r['loaded_vs_built']:+.1f} % against built)")
+        lines.append(f"    kernels: built [{r['kernels']['built']}]  loaded [{r['kernels']['loaded']}]")
+    open(out + ".txt", "w").write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+    return 0
+
+
 def main_index(args):
     results = {}
     for leg, limit in INDEX_LEG_SECONDS.items():
@@ -549,6 +643,7 @@ def main():
     ap.add_argument("--index", action="store_true", help="the sync index legs (i, j) instead of a-e")
     ap.add_argument("--delta", action="store_true", help="the variant store leg (k) instead of a-e")
     ap.add_argument("--digest", action="store_true", help="the content digest leg (m) instead of a-e")
+    ap.add_argument("--delta-file", action="store_true", help="the delta file leg (n) instead of a-e")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resident_decode"))
     args = ap.parse_args()
     if args.leg:                                          # a child: one leg, its result as one JSON line
@@ -560,6 +655,8 @@ def main():
         return main_delta(args)
     if args.digest:
         return main_digest(args)
+    if args.delta_file:
+        return main_delta_file(args)
     results = {}
     for leg, limit in LEG_SECONDS.items():
         p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--layers", str(args.layers), "--reps", str(args.reps)],

@@ -12,7 +12,9 @@ test-suite drives the emulated kernels, exactly as `CompressedSlice` does.
 import torch
 
 from . import _capi, codec
-from .zipnn import _ST_DTYPE_NAME, COMPRESSION_METHOD, ZipNN, dtype_from_user, index_rows
+from .header import HEADER_LEN, EnumFormat, pack_shape
+from .zipnn import (_ST_DTYPE_NAME, COMPRESSION_METHOD, ZipNN, build_compressed_tensor_info, dtype_from_user, index_rows,
+                    set_compressed_tensors_metadata)
 
 # (see ResidentCheckpoint.INDEX_DTYPES)
 _INDEX_DTYPES = (torch.bfloat16, torch.float16, torch.float32) + tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e5m2") if hasattr(torch, n))
@@ -57,14 +59,16 @@ class _Entry:
     """One tensor of the store: a frame body in device memory (`body`, with its codec parameters), or the tensor itself (`raw`).
     In a variant store (ResidentCheckpoint.from_state_dict(..., base=...)): `delta` is True where the body encodes tensor ^ base, "same" where the tensor's
     bytes are the base's (no body; `raw` is the base's own tensor where the base holds it plainly) and False otherwise; `base` is what a delta or "same" entry
-    decodes over and `restore` what revert_ puts back — ("tensor", the base's tensor, held by reference) or ("entry", the base store, its entry) — or None."""
-    __slots__ = ("name", "dtype", "shape", "nbytes", "body", "raw", "P", "bits", "byts", "chunk", "hints", "delta", "base", "restore")
+    decodes over and `restore` what revert_ puts back — ("tensor", the base's tensor, held by reference) or ("entry", the base store, its entry) — or None.
+    `head`: the first 16 bytes of the frame header the body was written behind or would be (magic … dtype code): what save_file writes in front of it again."""
+    __slots__ = ("name", "dtype", "shape", "nbytes", "body", "raw", "P", "bits", "byts", "chunk", "hints", "delta", "base", "restore", "head")
 
     def __init__(self, name, dtype, shape, nbytes, body=None, raw=None, params=None):
         self.name, self.dtype, self.shape, self.nbytes, self.body, self.raw = name, dtype, tuple(int(d) for d in shape), int(nbytes), body, raw
         self.hints = None                      # the body's decode hints (ResidentCheckpoint.build_index): a uint8 tensor beside the body, or None
         self.P, self.bits, self.byts, self.chunk = params if params is not None else (0, 0, 0, 0)
         self.delta, self.base, self.restore = False, None, None
+        self.head = None
 
     @property
     def compressed(self):
@@ -132,6 +136,7 @@ class ResidentCheckpoint:
         self._index = None                     # the allocation the entries' hints are views of (build_index)
         self._index_bytes = 0
         self._digests = None                   # {name: "zn64-1" digest of the tensor's bytes} when the store was built with digests, else None
+        self._metadata = None                  # from_file: the file's own metadata (without the keys this library writes), which save_file writes back
 
     # ---- constructors -------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -146,31 +151,94 @@ class ResidentCheckpoint:
         return dev
 
     @classmethod
-    def from_file(cls, path, device="cuda:0", index=False, digests=False, verify=False):
+    def from_file(cls, path, device="cuda:0", index=False, digests=False, verify=False, base=None, verify_base=True):
         """A `.znn.safetensors` file (this library's or the reference's): its data section goes to `device` once, in one transfer, and stays.
         index=True: build_index() on the new store.
         digests=True: the store records a content digest per tensor (digests(), verify(), holds()).  A file written with digests
         (compress_safetensors_file(..., digests=True)) brings them, and they are taken from it — they describe what the WRITER compressed.  A file
         without them is decoded once and the store records what it got: that only pins the state at load — damage that happened before is not seen.
         verify=True: the file's digests are checked against one decode of every tensor at load; DigestMismatch names the tensors that differ, and a file
-        without digests is an error, not a pass."""
+        without digests is an error, not a pass.
+
+        base: what a DELTA file (metadata key znn_delta; written by save_file of a variant store) was taken over — what from_state_dict accepts
+        as `base`: a store on the device, a mapping of names to device tensors, a module.  The result is the variant store from_state_dict(ft_sd, base=base)
+        would have built — the same info() for every tensor, the same bodies, now views of the uploaded data section — with no compression run and no tensor
+        of the fine-tune materialised.  A delta file without `base` is a ValueError, and so is a base that lacks a tensor the file codes over it, holds it with
+        another dtype or shape, or holds it compressed in chunks of another size (each names the tensor).  XOR over the wrong base decodes cleanly to garbage, so
+        with verify_base=True (the default) the base's digests are compared with the file's `base_digests` before anything is uploaded or decoded: a base
+        store's recorded digests are used as they are, a base without them is digested once, all its needed tensors in one batch (decoded, or where they lie);
+        DigestMismatch names the tensors that differ.  verify=True keeps its meaning: the decoded fine-tune against `znn_digests`.  A file that is no delta file
+        takes `base` only as what revert_ restores from."""
+        import json
         from . import safetensors_io
         dev = cls._work_device(device)
-        recorded = safetensors_io.file_digests(safetensors_io.read_metadata(path)) if (digests or verify) else None
+        meta = safetensors_io.read_metadata(path)
+        recorded = safetensors_io.file_digests(meta) if (digests or verify) else None
         if verify and recorded is None:
             raise ValueError(f"{path}: the file carries no digests (znn_digests): nothing to verify against")
-        up = safetensors_io._upload_file(path, dev)
+        delta = safetensors_io.file_delta(meta)
+        if delta is not None and base is None:
+            raise safetensors_io._needs_base(path)
+        based = cls._base_items(base, dev)
+        kinds, over = {}, {}                                           # {name: "delta" | "same"}, {name: (dtype, shape, what it is coded over)}
+        if delta is not None:
+            kinds, want = delta
+            infos = safetensors_io.get_compressed_tensors_metadata(meta)
+            for name in kinds:
+                if name not in infos:
+                    raise ValueError(f"{path}: {name!r} is listed under znn_delta but not under znn_compressed_vectors")
+                dt, shape = getattr(torch, str(infos[name].get("dtype")), None), tuple(int(d) for d in json.loads(infos[name].get("shape", "[]")))
+                if not isinstance(dt, torch.dtype):
+                    raise ValueError(f"{path}: {name!r}: unknown dtype {infos[name].get('dtype')!r}")
+                ref = based.get(name)
+                if ref is None:
+                    raise ValueError(f"{path}: the base has no tensor {name!r}, which the file codes over it")
+                b = ref[1] if ref[0] == "tensor" else ref[2]
+                if b.dtype != dt or tuple(b.shape) != shape:
+                    raise ValueError(f"{path}: {name!r} is {dt} {list(shape)} over a base tensor of the same dtype and shape; the base holds {b.dtype} {list(b.shape)}")
+                over[name] = (dt, shape, ref)
+            if verify_base:
+                got = cls._ref_digests({name: ref for name, (_, _, ref) in over.items()}, dev)
+                bad = [name for name in kinds if got[name] != want[name]]
+                if bad:
+                    raise codec.DigestMismatch(bad, f"{path}: the base does not hold what the delta was taken over")
+        up = safetensors_io._upload_file(path, dev, delta=delta is not None)
         if up is None:
             raise ValueError(f"{path}: the container names a dtype this loader does not know")
         layout, plan, blob = up.layout, up.frames, up.blob
         entries, framed, extra = [], {}, 0
         for (name, b0, hi, fp, _) in plan:
             _, P, bits, byts, chunk, n, tdt, shape = fp
-            framed[name] = _Entry(name, tdt, shape if shape is not None else (n // max(torch.empty(0, dtype=tdt).element_size(), 1),), n,
-                                  body=blob[b0:hi], params=(P, bits, byts, chunk))
+            head = up.heads.get(name)
+            is_delta = kinds.get(name) == "delta"
+            if head is not None and (head[9] != 0) != is_delta:
+                raise ValueError(f"{path}: {name!r}: the frame header says {'delta' if head[9] else 'no delta'}, znn_delta says otherwise")
+            if is_delta:
+                tdt, shape, ref = over[name]
+                if n != _numel(shape) * torch.empty(0, dtype=tdt).element_size():
+                    raise ValueError(f"{path}: {name!r}: a frame of {n} bytes for {tdt} {list(shape)}")
+                if ref[0] == "entry" and ref[2].chunk != chunk:
+                    raise ValueError(f"{path}: {name!r} is coded in chunks of {chunk} bytes, the base holds it in chunks of {ref[2].chunk}")
+            e = framed[name] = _Entry(name, tdt, shape if shape is not None else (n // max(torch.empty(0, dtype=tdt).element_size(), 1),), n,
+                                      body=blob[b0:hi], params=(P, bits, byts, chunk))
+            e.head = head
+            if is_delta:
+                e.delta, e.base = True, ref
         for name, (dt, shape, lo, hi) in layout.items():          # (file order)
             if name in framed:
                 entries.append(framed[name])
+                continue
+            if kinds.get(name) == "same":                          # nothing of its own: the base's tensor itself, or a decode of the base's body
+                tdt, tshape, ref = over[name]
+                if hi != lo:
+                    raise ValueError(f"{path}: {name!r} is listed as \"same\" but holds {hi - lo} bytes")
+                if ref[0] == "tensor":
+                    params = tuple(ZipNN(input_format="torch", bytearray_dtype=tdt, method=COMPRESSION_METHOD).torch_frame_plan(torch.empty(tshape, dtype=tdt, device="meta"))[1:])
+                else:
+                    params = (ref[2].P, ref[2].bits, ref[2].byts, ref[2].chunk)
+                e = _Entry(name, tdt, tshape, _numel(tshape) * torch.empty(0, dtype=tdt).element_size(), raw=ref[1] if ref[0] == "tensor" else None, params=params)
+                e.delta, e.base = "same", ref
+                entries.append(e)
                 continue
             if hi > lo:
                 es = torch.empty(0, dtype=dt).element_size()
@@ -182,7 +250,14 @@ class ResidentCheckpoint:
             else:
                 raw = torch.empty(shape, dtype=dt, device=dev)
             entries.append(_Entry(name, dt, shape, hi - lo, raw=raw))
-        store = cls(dev, entries, blob.numel() + extra, keep=(blob,))
+        for e in entries:                                          # what revert_ restores from: the base's tensor of the same name, dtype and shape
+            ref = based.get(e.name)
+            if ref is not None:
+                b = ref[1] if ref[0] == "tensor" else ref[2]
+                if b.dtype == e.dtype and tuple(b.shape) == e.shape:
+                    e.restore = ref
+        store = cls(dev, entries, blob.numel() + extra, keep=(blob,) + ((base,) if base is not None else ()))
+        store._metadata = {k: v for k, v in up.metadata.items() if k not in (safetensors_io.METADATA_KEY, safetensors_io.DIGESTS_KEY, safetensors_io.DELTA_KEY)}
         if index:
             store.build_index()
         if recorded is not None:
@@ -195,6 +270,27 @@ class ResidentCheckpoint:
         elif digests:
             store._digests = store._decoded_digests(store.keys())
         return store
+
+    @staticmethod
+    def _ref_digests(refs, dev):
+        """{name: ("tensor", tensor) | ("entry", store, entry)} (_base_items) -> {name: digest of that base tensor's bytes}: a base store's recorded digest where
+        it has one; otherwise the plain tensors digested where they lie, all in one batched launch, and a store's entries through one _decoded_digests call."""
+        out, live, via = {}, [], {}
+        for name, ref in refs.items():
+            if ref[0] == "tensor":
+                live.append((name, ref[1]))
+            elif ref[1]._digests is not None:
+                out[name] = ref[1]._digests[ref[2].name]
+            else:
+                via.setdefault(id(ref[1]), (ref[1], []))[1].append((name, ref[2].name))
+        if live:
+            with _device_of(dev):
+                vals = codec.digests_to_ints(codec.digest_device_batch(_capi.lib(), [codec.flat_bytes(t) for _, t in live], _stream_of(dev)))
+            out.update({name: v for (name, _), v in zip(live, vals)})
+        for bstore, pairs in via.values():
+            got = bstore._decoded_digests([bn for _, bn in pairs])
+            out.update({name: got[bn] for name, bn in pairs})
+        return out
 
     @staticmethod
     def _base_items(base, dev):
@@ -245,14 +341,20 @@ class ResidentCheckpoint:
         todo, entries = [], {}
         coders = {}                            # one ZipNN per dtype: what decides a tensor's frame parameters
 
-        def frame_params(t):
+        heads = {}                             # {name: the first 16 bytes of the frame header that describes the tensor's body}
+
+        def frame_plan(t):
             if t.dtype not in coders:
                 coders[t.dtype] = ZipNN(input_format="torch", bytearray_dtype=t.dtype, method=method or COMPRESSION_METHOD)
-            return tuple(coders[t.dtype].torch_frame_plan(t)[1:])
+            return coders[t.dtype].torch_frame_plan(t)
+
+        def frame_params(t):
+            return tuple(frame_plan(t)[1:])
         for name, t in sd.items():
             t = t.detach()
             if torch.is_floating_point(t) and t.dtype != torch.float64 and t.numel() > 0 and dtype_from_user(t.dtype) is not None:
-                P, bits, byts, chunk = frame_params(t)
+                hdr, P, bits, byts, chunk = frame_plan(t)
+                heads[name] = bytes(hdr[:16])
                 todo.append((name, t.to(dev), (P, bits, byts, chunk)))
             else:
                 entries[name] = _Entry(name, t.dtype, t.shape, t.numel() * t.element_size(), raw=t.to(dev).clone())
@@ -348,6 +450,8 @@ class ResidentCheckpoint:
         held += sum(e.nbytes for e in entries.values() if not e.compressed and e.delta != "same")
         if base is not None:
             keep.append(base)
+        for name, h in heads.items():
+            entries[name].head = h
         store = cls(dev, [entries[name] for name in sd.keys()], held, keep=keep)
         store._digests = recorded
         if index:
@@ -491,6 +595,89 @@ class ResidentCheckpoint:
     def resident_bytes(self):
         """Bytes of device memory the store holds."""
         return self._held
+
+    # ---- writing the store down (DESIGN §3.9) -----------------------------------------------------------------------------------
+    def _frame_header(self, e):
+        """-> the frame header save_file writes in front of e's body: the torch-format header (with the shape extension) of a plain body — what
+        compress_safetensors_file writes —, the BYTE-format header with the delta flag (byte 9 = 1, no shape extension) of a delta body: the form the
+        reference's delta decode takes.  Bytes 0-15 are the entry's own (version, method, reorder modes, chunk exponent, dtype code)."""
+        head = e.head
+        if head is None:
+            head = ZipNN(input_format="torch", bytearray_dtype=e.dtype, method=COMPRESSION_METHOD).torch_frame_plan(torch.empty(e.shape, dtype=e.dtype, device="meta"))[0][:16]
+        h = bytearray(HEADER_LEN)
+        h[:16] = head
+        h[8], h[9] = (EnumFormat.BYTE.value, 1) if e.delta is True else (EnumFormat.TORCH.value, 0)
+        ext = b"" if e.delta is True else pack_shape(e.shape)
+        h[16:24] = e.nbytes.to_bytes(8, "little")
+        h[24:32] = (HEADER_LEN + len(ext) + e.body.numel()).to_bytes(8, "little")      # (the total length, as the core writes it)
+        return bytes(h) + ext
+
+    def save_file(self, path, digests=None, metadata=None):
+        """Write the store as a `.znn.safetensors` file -> path.  Any store: plain, indexed, a variant, a variant of a variant.  The bodies go out as they lie in
+        device memory — one transfer to the host per allocation that holds them (one for a store from from_state_dict or from_file), never recompressed —,
+        each behind the frame header that describes its parameters; a tensor whose header + body would not be smaller than the tensor is written as it is
+        (the rule of compress_safetensors_file; it costs one decode of that tensor), and so is every tensor the store holds plainly.  A plain store's file is
+        the file compress_safetensors_file writes for the same tensors, byte for byte.
+        A VARIANT writes a delta file: the metadata key `znn_delta` lists the tensors coded over the base — "delta": the frame's body is tensor ^ base, its
+        header the byte-format one with the delta flag; "same": a zero-length entry, the tensor is the base's — and `base_digests`, the content digests of the
+        BASE's tensors: a base store's recorded ones, else one batched digest of the base's decoded or live tensors.  Read it back with
+        from_file(path, device, base=...) / safetensors_io.load_file(path, device, base=...).
+        digests: None writes `znn_digests` when the store has digests; True computes them (one decode of every tensor) where it has none; False omits them.
+        metadata: the file's other metadata (default: what from_file found in the store's own file, else {"format": "pt"}).  The sync index is not saved:
+        from_file(index=True) rebuilds it."""
+        from safetensors.torch import save_file as st_save_file
+        from . import safetensors_io
+        lib = _capi.lib()
+        recorded = None
+        if digests or (digests is None and self._digests is not None):
+            recorded = self._digests if self._digests is not None else self._decoded_digests(self.keys())
+        # which bodies go out as frames, and the one trip of each allocation that holds them
+        framed, roots = {}, {}
+        for e in self._entries.values():
+            if e.compressed:
+                hdr = self._frame_header(e)
+                if len(hdr) + e.body.numel() < e.nbytes:
+                    root = e.body._base if e.body._base is not None else e.body
+                    off = e.body.storage_offset() - root.storage_offset()
+                    key = (root.data_ptr(), root.numel())
+                    span = roots.setdefault(key, [root, off, off + e.body.numel()])
+                    span[1], span[2] = min(span[1], off), max(span[2], off + e.body.numel())
+                    framed[e.name] = (hdr, key, off)
+        host = {}
+        with _device_of(self.device):
+            for key, (root, lo, hi) in roots.items():
+                host[key] = (memoryview(codec.to_host(lib, root.reshape(-1)[lo:hi])), lo)
+        tensors, infos, kinds, refs = {}, {}, {}, {}
+        order = sorted(self._entries)                              # (the order safetensors walks a file's names in: the metadata lists keep it, as compress_safetensors_file's do)
+        for name in order:
+            e = self._entries[name]
+            like = torch.empty(e.shape, dtype=e.dtype, device="meta")
+            if name in framed:
+                hdr, key, off = framed[name]
+                mv, lo = host[key]
+                frame = codec.new_bytearray(len(hdr) + e.body.numel())
+                frame[:len(hdr)] = hdr
+                frame[len(hdr):] = mv[off - lo: off - lo + e.body.numel()]
+                tensors[name] = torch.frombuffer(frame, dtype=torch.uint8)
+                infos[name] = build_compressed_tensor_info(like)
+                if e.delta is True:
+                    kinds[name], refs[name] = "delta", e.base
+            elif e.delta == "same":
+                tensors[name] = torch.empty(0, dtype=torch.uint8)
+                infos[name] = build_compressed_tensor_info(like)
+                kinds[name], refs[name] = "same", e.base
+            else:
+                tensors[name] = (self.get_tensor(name) if e.decoded else e.raw).detach().cpu().contiguous()
+        metadata = dict(metadata) if metadata is not None else dict(self._metadata or {})
+        if not metadata:
+            metadata = {"format": "pt"}
+        set_compressed_tensors_metadata(infos, metadata)
+        if recorded is not None:
+            safetensors_io._set_digests_metadata(metadata, order, [recorded[n] for n in order])
+        if kinds:
+            safetensors_io._set_delta_metadata(metadata, kinds, self._ref_digests(refs, self.device))
+        st_save_file(tensors, path, metadata)
+        return path
 
     # ---- decoding -------------------------------------------------------------------------------------------------------------
     def scratch_bytes(self, names):

@@ -15,6 +15,9 @@ from .zipnn import (COMPRESSED_DTYPE, COMPRESSION_METHOD, METADATA_KEY, ZipNN, b
 SUFFIX = ".znn.safetensors"
 _DIGEST_GROUP_BYTES = 256 << 20      # compress_safetensors_file(digests=True), per-tensor path: tensors are digested as they are read, in groups of at most this many bytes
 DIGESTS_KEY = "znn_digests"          # file metadata: a JSON string {"algo": "zn64-1", "tensors": {name: 16 hex digits}} — digests of the DECODED bytes of every tensor
+DELTA_KEY = "znn_delta"              # file metadata of a DELTA file: a JSON string {"version": 1, "algo": "zn64-1", "tensors": {name: "delta" | "same"},
+                                     # "base_digests": {name: 16 hex digits}} — which tensors are coded over a base, and the digests of that base's tensors
+DELTA_VERSION = 1
 
 
 def read_metadata(filename):
@@ -38,6 +41,41 @@ def file_digests(metadata):
     return {name: int(h, 16) for name, h in d["tensors"].items()}
 
 
+def file_delta(metadata):
+    """-> ({name: "delta" | "same"}, {name: digest of the BASE tensor's bytes}) from a delta file's metadata, or None for a file that is no delta file.
+    A version or a digest algorithm this library does not know, or an entry without its base digest, is an error."""
+    import json
+    from . import codec
+    raw = metadata.get(DELTA_KEY)
+    if raw is None:
+        return None
+    d = json.loads(raw)
+    if d.get("version") != DELTA_VERSION:
+        raise ValueError(f"{DELTA_KEY}: unknown version {d.get('version')!r} (this library knows {DELTA_VERSION})")
+    if d.get("algo") != codec.DIGEST_ALGO:
+        raise ValueError(f"{DELTA_KEY}: unknown digest algorithm {d.get('algo')!r} (this library knows {codec.DIGEST_ALGO!r})")
+    kinds = dict(d.get("tensors") or {})
+    odd = [n for n, k in kinds.items() if k not in ("delta", "same")]
+    if odd:
+        raise ValueError(f"{DELTA_KEY}: {odd[0]!r} is neither \"delta\" nor \"same\"")
+    base = {name: int(h, 16) for name, h in (d.get("base_digests") or {}).items()}
+    missing = [n for n in kinds if n not in base]
+    if missing:
+        raise ValueError(f"{DELTA_KEY}: base_digests lacks {missing[:3]}{' …' if len(missing) > 3 else ''}")
+    return kinds, base
+
+
+def _set_delta_metadata(metadata, kinds, base_digests):
+    import json
+    from . import codec
+    metadata[DELTA_KEY] = json.dumps({"version": DELTA_VERSION, "algo": codec.DIGEST_ALGO, "tensors": dict(kinds),
+                                      "base_digests": {n: f"{base_digests[n]:016x}" for n in kinds}})
+
+
+def _needs_base(filename):
+    return ValueError(f"{filename}: a delta file ({DELTA_KEY}): its tensors are coded over a base — load it with load_file(base=) / ResidentCheckpoint.from_file(base=)")
+
+
 def _set_digests_metadata(metadata, names, values):
     import json
     from . import codec
@@ -57,18 +95,23 @@ def check_digests(tensors, want, what):
         raise codec.DigestMismatch(bad, f"{what}: decoded bytes differ from the file's digests")
 
 
-def compress_safetensors_file(filename, out_path=None, device="cpu", method=None, batched=None, digests=False):
+def compress_safetensors_file(filename, out_path=None, device="cpu", method=None, batched=None, digests=False, base=None):
     """-> path of the compressed file.  `device` = where tensors are staged for compression
     ("cuda:N" compresses in HBM; the compressed frames come back to the host for writing).  Tensors staged in HBM
     are compressed by ONE batched call for the whole file (`batched=None`: automatic; True forces it).
     digests=True: the metadata also gets `znn_digests`, the content digest ("zn64-1") of every tensor's bytes, compressed or not, taken from the SOURCE
     tensors (on the device path in one launch over the uploaded data section; on the per-tensor path as they are read, a group of at most 256 MiB — or one larger
     tensor — at a time, which is all the option holds beyond the compression's own memory): load_file(..., verify=True) and ResidentCheckpoint.from_file check decodes against
-    it.  Readers that do not know the key ignore it; with the default the file is byte for byte what it was without this option."""
+    it.  Readers that do not know the key ignore it; with the default the file is byte for byte what it was without this option.
+    base: write a DELTA file over it — a path to the base's `.safetensors` or `.znn.safetensors`, a ResidentCheckpoint on the device, or a mapping
+    of names to device tensors: the file's tensors go to the device, become a variant store over the base (ResidentCheckpoint.from_state_dict(base=)) and that
+    store is saved (ResidentCheckpoint.save_file).  A device is needed for it: with device="cpu" the current GPU is used."""
     from safetensors import safe_open
     from safetensors.torch import save_file
     assert filename.endswith(".safetensors")
     out_path = out_path or filename[: -len(".safetensors")] + SUFFIX
+    if base is not None:
+        return _compress_file_over_base(filename, out_path, device, method, digests, base)
     if torch.device(device).type == "cuda" and batched is not False:
         done = _compress_file_on_device(filename, out_path, torch.device(device), method, digests)
         if done is not None:
@@ -128,6 +171,36 @@ def compress_safetensors_file(filename, out_path=None, device="cpu", method=None
         _set_digests_metadata(metadata, list(recorded.keys()), list(recorded.values()))
     save_file(tensors, out_path, metadata)
     return out_path
+
+
+def _base_store(base, dev):
+    """`base` given as a path -> a resident store of that file (plain or compressed) on `dev`; anything else as it is."""
+    if isinstance(base, (str, os.PathLike)):
+        from .resident import ResidentCheckpoint
+        return ResidentCheckpoint.from_file(os.fspath(base), dev)
+    return base
+
+
+def _compress_file_over_base(filename, out_path, device, method, digests, base):
+    """compress_safetensors_file(base=): file -> delta file, through the store path (no second writer)."""
+    from . import codec
+    from .resident import ResidentCheckpoint
+    dev = torch.device(device)
+    if dev.type != "cuda" and torch.cuda.is_available():
+        dev = torch.device("cuda", codec.current_device())
+    dev = ResidentCheckpoint._work_device(dev)
+    tensors = load_file(filename, dev)
+    store = ResidentCheckpoint.from_state_dict(tensors, dev, method=method, base=_base_store(base, dev), digests=bool(digests))
+    del tensors
+    return store.save_file(out_path, digests=bool(digests), metadata=read_metadata(filename) or None)
+
+
+def save_file(tensors, filename, device="cuda:0", base=None, digests=False, metadata=None):
+    """safetensors.torch.save_file for live tensors, compressed: ResidentCheckpoint.from_state_dict(tensors, device, base=base, digests=digests) followed by its
+    save_file — with `base` (a store on the device, a mapping of device tensors, a module) a DELTA file over it.  -> filename."""
+    from .resident import ResidentCheckpoint
+    store = ResidentCheckpoint.from_state_dict(tensors, device, base=base, digests=bool(digests))
+    return store.save_file(filename, digests=bool(digests), metadata=metadata)
 
 
 def _compress_file_on_device(filename, out_path, dev, method, digests=False):
@@ -291,9 +364,9 @@ def decode_file_on_device(filename, device, compressed_only=False, timings=None,
 
 class _Uploaded:
     """A .znn.safetensors file whose data section is on the device (_upload_file)."""
-    __slots__ = ("device", "layout", "infos", "frames", "arena_bytes", "blob", "marks")
+    __slots__ = ("device", "layout", "infos", "frames", "arena_bytes", "blob", "marks", "metadata", "heads")
 
-    def __init__(self, device, layout, infos, frames, arena_bytes, blob, marks):
+    def __init__(self, device, layout, infos, frames, arena_bytes, blob, marks, metadata=None, heads=None):
         self.device = device              # torch.device
         self.layout = layout              # {name: (dtype, shape, lo, hi)}: every tensor of the container, offsets into blob
         self.infos = infos                # the file's znn_compressed_vectors metadata
@@ -301,12 +374,14 @@ class _Uploaded:
         self.arena_bytes = arena_bytes    # size of an arena that takes every decoded tensor at a 256-byte boundary
         self.blob = blob                  # the data section: a uint8 tensor on the device
         self.marks = marks                # perf_counter at start / headers parsed / upload done
+        self.metadata = metadata or {}    # the file's __metadata__
+        self.heads = heads or {}          # per compressed tensor: the first 16 bytes of its frame header (magic … dtype code)
 
 
-def _upload_file(filename, device):
+def _upload_file(filename, device, delta=False):
     """First half of decode_file_on_device, and how resident.ResidentCheckpoint.from_file gets its frames into HBM: every frame header parsed
     from the host mapping, then the file's data section to the device in ONE transfer.  -> _Uploaded, or None when the container names a dtype
-    this parser does not know."""
+    this parser does not know.  A delta file (znn_delta) is refused unless the caller says it brings the base (delta=True): its "same" entries hold no frame."""
     import contextlib
     import mmap
     import threading
@@ -323,6 +398,10 @@ def _upload_file(filename, device):
     t0 = time.perf_counter()
     metadata, layout, data_start = lay
     infos = get_compressed_tensors_metadata(dict(metadata))
+    kinds = file_delta(metadata)
+    if kinds is not None and not delta:
+        raise _needs_base(filename)
+    skip = frozenset(n for n, k in kinds[0].items() if k == "same") if kinds is not None else ()
     with open(filename, "rb") as f:
         size = os.fstat(f.fileno()).st_size
         mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if size else None
@@ -330,10 +409,11 @@ def _upload_file(filename, device):
     head_len = 32 + 1 + 9 * 255                        # header + the largest shape extension (zipnn._frame_head)
     try:
         # ---- host side: one pass over the mapping ----
-        plan, total = [], 0                            # (name, lo + body_off, hi, fp, arena offset)
+        plan, total, heads = [], 0, {}                 # (name, lo + body_off, hi, fp, arena offset)
         for name, (dt, shape, lo, hi) in layout.items():
-            if name in infos:
+            if name in infos and name not in skip:
                 fp = fast_frame_params(view[data_start + lo: data_start + min(hi, lo + head_len)])
+                heads[name] = bytes(view[data_start + lo: data_start + lo + 16])
                 plan.append((name, lo + fp[0], hi, fp, total))
                 total += (fp[5] + 255) & ~255
         t1 = time.perf_counter()
@@ -355,7 +435,7 @@ def _upload_file(filename, device):
             closer = threading.Thread(target=_close_mapping, daemon=True)
             closer.start()
             _PENDING_CLOSERS.append(closer)                # (joined by the next call — by then long finished — not by this one: nothing below needs the mapping gone)
-    return _Uploaded(dev, layout, infos, plan, total, blob, (t0, t1, t2))
+    return _Uploaded(dev, layout, infos, plan, total, blob, (t0, t1, t2), dict(metadata), heads)
 
 
 def _decode_uploaded(lib, codec, dev, layout, infos, plan, total, blob, use_arena, compressed_only, timings, marks):
@@ -413,7 +493,7 @@ def _decode_uploaded(lib, codec, dev, layout, infos, plan, total, blob, use_aren
     return out
 
 
-def load_file(filename, device="cuda:0", timings=None, verify=False):
+def load_file(filename, device="cuda:0", timings=None, verify=False, base=None, verify_base=True):
     """Load a (possibly ZipNN-compressed) safetensors file straight onto `device` -> {name: tensor}: one transfer of the file's data
     section, one batched decode (decode_file_on_device).  The batched counterpart of looping SafeOpen.get_tensor (reference
     zipnn.py:1592-1626, scripts/zipnn_decompress_safetensors.py:75-120) — and what SafeOpen itself uses behind get_tensor for a
@@ -421,13 +501,27 @@ def load_file(filename, device="cuda:0", timings=None, verify=False):
     moving the data section to the device (`h2d_s`) and decoding (`decode_s`), each ended by a device sync.
     verify=True: the decoded tensors are digested — on a GPU all of them by one batched launch, with device="cpu" by the host function — and compared with
     the file's `znn_digests` (compress_safetensors_file(..., digests=True)); DigestMismatch names the tensors that differ.  A file without digests is an
-    error then, not a pass."""
+    error then, not a pass.
+    base: what a DELTA file (znn_delta) was taken over — a ResidentCheckpoint on the device, a mapping of names to device tensors, a module, or
+    a path to the base's file, plain or compressed.  The file becomes a variant store over it (ResidentCheckpoint.from_file(base=), which checks the base's
+    digests against the file's unless verify_base=False) and every tensor is decoded once; plain tensors come back, none of them the base's own.  A delta
+    file without `base` is a ValueError; a file that is no delta file does not look at `base`."""
     dev = torch.device(device)
     want = None
+    meta = read_metadata(filename) if (verify or base is not None) else {}
     if verify:
-        want = file_digests(read_metadata(filename))
+        want = file_digests(meta)
         if want is None:
             raise ValueError(f"{filename}: the file carries no digests ({DIGESTS_KEY}): nothing to verify against")
+    if base is not None and DELTA_KEY in meta:
+        from .resident import ResidentCheckpoint
+        dev = ResidentCheckpoint._work_device(dev)
+        store = ResidentCheckpoint.from_file(filename, dev, base=_base_store(base, dev), verify_base=verify_base)
+        got = store.get_tensors(store.keys())
+        out = {n: (t if store._entries[n].decoded else t.clone()) for n, t in got.items()}      # (no view of the uploaded section, no tensor of the base)
+        if want is not None:
+            check_digests(out, want, filename)
+        return out
     out = decode_file_on_device(filename, dev, timings=timings)
     if out is None:
         out = _load_file_per_tensor(filename, dev, timings)

@@ -724,6 +724,9 @@ class SafeOpen:
         self._f = _ORIGINAL_SAFE_OPEN(filename, framework=framework, device=device, **kwargs)
         self._host = None
         self._filename, self._framework, self._kwargs = filename, framework, kwargs
+        if "znn_delta" in (self._f.metadata() or {}):
+            # a delta file: its tensors are coded over a base this interface has no way to be given — refused at open, never decoded wrongly
+            raise ValueError(f"{filename}: a delta file (znn_delta): its tensors are coded over a base — load it with zipnn_amd.safetensors_io.load_file(base=)")
         self.compressed_tensors_metadata = get_compressed_tensors_metadata(self._f.metadata())
         self._ahead = None                 # read-ahead cache {name: decoded tensor}; False = not applicable for this file
 
