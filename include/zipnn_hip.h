@@ -168,7 +168,7 @@ int zn_plan_destroy(zn_plan* plan);
  * it had when the index was built, decoded by the library build that built it (a resident store guarantees both).  Anything else is only slower.
  * What reads hints: the fused kernel's full-chunk workgroups in calls WITHOUT a delta base that do not take the small-input (wide) form — zn_set_decode_wide's
  * automatic rule decides that as for any call, before hints are looked at.  Partial last chunks, further Huffman planes of a chunk, the generic path and items
- * with a delta base (which make their whole launch unhinted) decode as they always do.
+ * with a delta base (which make their whole launch unhinted — for an index of THIS kind; ZN_HINT_DELTA below is the kind such items read) decode as they always do.
  * zn_hint_size_dev: the index's length for the WHOLE body of `item` (chunk_lo / chunk_hi / d_dst / d_delta are ignored) — one small launch, one 8-byte read-back.
  * zn_hint_build_dev: fills d_hints (16-byte aligned; hint_cap >= that length, else ZN_E_ARG); synchronous; device scratch: a byte per (plane, chunk).
  * A hinted item is a window item plus its body's index (NULL / 0: none; a hint_len below zn_hint_size_dev's answer, NULL with a length, or an unaligned
@@ -185,6 +185,30 @@ int zn_hint_size_dev(const zn_window_item* item, size_t* hint_bytes, void* strea
 int zn_hint_build_dev(const zn_window_item* item, void* d_hints, size_t hint_cap, void* stream);
 int zn_decompress_hinted_batch_dev(const zn_hinted_item* items, size_t count, void* stream, int check);
 int zn_plan_create_hinted(const zn_hinted_item* items, size_t count, zn_plan** plan);
+/* Index KINDS.  The four functions above make and read indexes of kind ZN_HINT_PLAIN: for bodies decoded WITHOUT a delta base.  A body that holds tensor ^ base (a
+ * fine-tune kept as a delta, decoded with d_delta set) is decoded by other instances of the fused kernel — they choose other sub-block sizes, and every plane of
+ * such a body compresses, so that the planes behind the first Huffman-coded one are decoded by further passes.  ZN_HINT_DELTA is the index for them: the same
+ * container (offset table, 64-byte padding, hint bytes; four streams one behind the other per region), in which EVERY Huffman-coded plane of a full chunk the
+ * fused kernel takes has a region — a plane without one has an empty region, table entry == the next entry — and whose bytes are valid for the delta instances'
+ * sub-block sizes: it is built by those instances (without a base: the build needs none and writes no rows) and read by them, separate destination, plain base
+ * tensor or IN PLACE (below), the undo of a chunk handed down included.
+ * WHICH INDEX IS READ: an item reads its index iff (kind == ZN_HINT_DELTA) == (item.d_delta != NULL).  A launch that has a delta base anywhere among its items
+ * of one plane count runs the delta instances for all of them and reads DELTA indexes only; a PLAIN index beside a delta base, a DELTA index beside none, or any
+ * index in a call that takes the small-input form decodes unhinted, exactly as before.  Either kind is ADVICE with the guarantees stated above; an index of one
+ * kind handed over as the other costs time at most.  The argument checks are those of the functions above, against the length zn_hint_size_dev2 gives for the
+ * KIND named; a kind other than these two is ZN_E_ARG.  zn_hint_size_dev / zn_hint_build_dev / zn_decompress_hinted_batch_dev / zn_plan_create_hinted are
+ * kind ZN_HINT_PLAIN of the functions below, byte for byte.  Not hinted, in either kind: partial last chunks and the small-input (wide) form. */
+#define ZN_HINT_PLAIN 0
+#define ZN_HINT_DELTA 1
+typedef struct zn_hinted_item2 {
+  zn_window_item item;
+  const void* d_hints; size_t hint_len;
+  int kind;                                 /* ZN_HINT_PLAIN / ZN_HINT_DELTA: what d_hints was built as */
+} zn_hinted_item2;
+int zn_hint_size_dev2(const zn_window_item* item, int kind, size_t* hint_bytes, void* stream);
+int zn_hint_build_dev2(const zn_window_item* item, int kind, void* d_hints, size_t hint_cap, void* stream);
+int zn_decompress_hinted_batch_dev2(const zn_hinted_item2* items, size_t count, void* stream, int check);
+int zn_plan_create_hinted2(const zn_hinted_item2* items, size_t count, zn_plan** plan);
 
 /* Delta ("byte"/"file" delta_compressed_type of the reference, zipnn/zipnn.py:625-640 and :983-1004: the bytes
  * are XORed with a second buffer of the same length before compression and after decompression).  The XOR is

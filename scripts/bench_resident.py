@@ -31,6 +31,9 @@ blocks of leg b as the base, the two fine-tunes of --delta:
      base=store) against from_state_dict(ft_sd, base=store) with ft_sd already on the device; from_file with verify_base over a base store with recorded
      digests, over one without, and with verify_base=False; plan.run of one block from the built variant and from the loaded one, interleaved (A B A B: the
      built variant's two runs are the A/A spread — the two run the same kernels on byte-equal bodies)
+--delta-index: the sync index of variant stores instead (build_index(deltas=True), DESIGN §3.6 "Two kinds"), into profiles/resident_delta_index.{json,txt}:
+  p  per fine-tune of --delta: plan.run of one block from a variant over a resident indexed base, without and with the variant's DELTA index, interleaved in
+     both orders (A B A B B A B A: the four runs without are the A/A spread), the build time of the DELTA index and its size
 """
 import argparse
 import json
@@ -604,6 +607,74 @@ def main_delta_file(args):
     return 0
 
 
+def leg_p(args):
+    """--delta-index: plan.run of one Llama-3-8B-shaped block from a variant over a resident INDEXED base, without and with the variant's DELTA index
+    — interleaved, both orders (A B A B, then B A B A) —, the build time of that index and its size."""
+    import torch
+    from zipnn_amd import ResidentCheckpoint
+    sd, per = _blocks(args.layers)
+    names = per[0]
+    res = {"layers": args.layers, "block_bytes": sum(sd[k].numel() * 2 for k in names), "fine_tunes": []}
+    base = ResidentCheckpoint.from_state_dict(sd, "cuda:0", index=True)
+    for kind in ("sparse", "drift"):
+        ft = _fine_tune(sd, kind, 21)
+        store = ResidentCheckpoint.from_state_dict(ft, "cuda:0", base=base, index=True)
+        dn = [k for k in names if store.info(k)["delta"] is True]
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        added = store.build_index(deltas=True)
+        torch.cuda.synchronize(); build_s = time.perf_counter() - t0
+        hints = {k: store._entries[k].hints for k in dn}
+        scratch = torch.empty(store.scratch_bytes(names), dtype=torch.uint8, device="cuda")
+        runs, kernels = {"plain": [], "hinted": []}, {}
+        for leg in ("plain", "hinted", "plain", "hinted", "hinted", "plain", "hinted", "plain"):
+            for k in dn:
+                store._entries[k].hints = hints[k] if leg == "hinted" else None
+            plan = store.plan(names, into=scratch)
+            t = _events_ms(plan.run, args.reps)
+            plan.status()
+            for k in names:
+                assert _same(plan.tensors[k], ft[k]), (kind, leg, k)
+            runs[leg].append(t["median_ms"])
+            kernels[leg] = _capi_kernels()
+            plan.close()
+        for k in dn:
+            store._entries[k].hints = hints[k]
+        a, h = runs["plain"], runs["hinted"]
+        dbytes = sum(store.info(k)["nbytes"] for k in dn)
+        res["fine_tunes"].append({"kind": kind, "delta_entries": len(dn), "tensors": len(names), "plan_run_ms": runs, "kernels": kernels,
+                                  "aa_spread": (max(a) - min(a)) / min(a), "gain": 1.0 - (sum(h) / len(h)) / (sum(a) / len(a)),
+                                  "delta_index_bytes": added, "delta_index_share": added / max(sum(store.info(k)["nbytes"] for k in store.keys() if store.info(k)["delta"] is True), 1),
+                                  "build_s": build_s, "block_delta_bytes": dbytes})
+        del store, ft, scratch
+        torch.cuda.empty_cache()
+    return res
+
+
+def main_delta_index(args):
+    p = subprocess.run(["timeout", "-k", "10", "540", sys.executable, os.path.abspath(__file__), "--leg", "p", "--layers", str(args.layers), "--reps", str(args.reps)],
+                       capture_output=True, text=True)
+    line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+    if p.returncode != 0 or not line:
+        print(f"leg p failed (exit {p.returncode})\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}")
+        return 1
+    res = json.loads(line[0][7:])
+    out = args.out if args.out != os.path.join(ROOT, "profiles", "resident_decode") else os.path.join(ROOT, "profiles", "resident_delta_index")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    lines = [f"command: python scripts/bench_resident.py --delta-index --layers {args.layers} --reps {args.reps}",
+             "DELTA sync index probe (ResidentCheckpoint.build_index(deltas=True)): plan.run of one Llama-3-8B block (bf16) from a variant over a resident indexed base,",
+             "without / with the variant's DELTA index, interleaved in both orders (A B A B B A B A), device events, median ms; every result checked against the fine-tune"]
+    for r in res["fine_tunes"]:
+        q = r["plan_run_ms"]
+        lines.append(f"  {r['kind']:<7} ({r['delta_entries']} of {r['tensors']} tensors of the block are delta entries): without " + " / ".join(f"{x:.4f}" for x in q["plain"]) +
+                     "   with " + " / ".join(f"{x:.4f}" for x in q["hinted"]) + f"   gain {100 * r['gain']:+.1f} %  (A/A spread of the runs without: {100 * r['aa_spread']:.1f} %)")
+        lines.append(f"          DELTA index of the store {r['delta_index_bytes']} B = {100 * r['delta_index_share']:.2f} % of the delta-coded tensors, built in {r['build_s']:.3f} s")
+        lines.append(f"          kernels without [{r['kernels']['plain']}]  with [{r['kernels']['hinted']}]")
+    open(out + ".txt", "w").write("\n".join(lines) + "\n")
+    json.dump(res, open(out + ".json", "w"), indent=1)
+    print("\n".join(lines))
+    return 0
+
+
 def main_index(args):
     results = {}
     for leg, limit in INDEX_LEG_SECONDS.items():
@@ -644,6 +715,7 @@ def main():
     ap.add_argument("--delta", action="store_true", help="the variant store leg (k) instead of a-e")
     ap.add_argument("--digest", action="store_true", help="the content digest leg (m) instead of a-e")
     ap.add_argument("--delta-file", action="store_true", help="the delta file leg (n) instead of a-e")
+    ap.add_argument("--delta-index", action="store_true", help="the DELTA sync index leg (p) instead of a-e")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resident_decode"))
     args = ap.parse_args()
     if args.leg:                                          # a child: one leg, its result as one JSON line
@@ -657,6 +729,8 @@ def main():
         return main_digest(args)
     if args.delta_file:
         return main_delta_file(args)
+    if args.delta_index:
+        return main_delta_index(args)
     results = {}
     for leg, limit in LEG_SECONDS.items():
         p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--layers", str(args.layers), "--reps", str(args.reps)],

@@ -25,6 +25,12 @@ HOT = [("zn_k_decode_fusedILi1ELb0ELb0E", "decode_fused<1> plain"), ("zn_k_decod
        ("zn_k_decode_fusedILi2ELb1ELb1E", "decode_fused<2> delta, in place"), ("zn_k_decode_fusedILi4ELb1ELb1E", "decode_fused<4> delta, in place"),
        ("zn_k_decode_hintedILi1ELb0ELb0ELi1E", "decode_hinted<1> read"), ("zn_k_decode_hintedILi2ELb0ELb0ELi1E", "decode_hinted<2> read"),
        ("zn_k_decode_hintedILi4ELb0ELb0ELi1E", "decode_hinted<4> read"), ("zn_k_decode_hintedILi2ELb0ELb0ELi2E", "decode_hinted<2> build"),
+       # the instances of indexes of kind ZN_HINT_DELTA
+       ("zn_k_decode_hintedILi1ELb1ELb0ELi1E", "decode_hinted<1> delta read"), ("zn_k_decode_hintedILi2ELb1ELb0ELi1E", "decode_hinted<2> delta read"),
+       ("zn_k_decode_hintedILi4ELb1ELb0ELi1E", "decode_hinted<4> delta read"),
+       ("zn_k_decode_hintedILi2ELb1ELb1ELi1E", "decode_hinted<2> delta read, in place"), ("zn_k_decode_hintedILi4ELb1ELb1ELi1E", "decode_hinted<4> delta read, in place"),
+       ("zn_k_decode_hintedILi1ELb1ELb0ELi2E", "decode_hinted<1> delta build"), ("zn_k_decode_hintedILi2ELb1ELb0ELi2E", "decode_hinted<2> delta build"),
+       ("zn_k_decode_hintedILi4ELb1ELb0ELi2E", "decode_hinted<4> delta build"),
        ("zn_k_decode_wideILi2ELi4E", "decode_wide<2> 16 waves"), ("zn_k_decode_wideILi2ELi2E", "decode_wide<2> 8 waves"),
        ("zn_k_encode_statsILi2ELb0E", "encode_stats<2>"), ("zn_k_encode_emitILi2ELb0E", "encode_emit<2>"), ("zn_k_encode_onepassILi2ELb0E", "encode_onepass<2>"),
        ("zn_k_encode_tables", "encode_tables"),

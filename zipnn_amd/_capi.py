@@ -56,6 +56,17 @@ class ZnHintedItem(ctypes.Structure):
 
 assert ctypes.sizeof(ZnHintedItem) == 96
 
+#: index kinds (include/zipnn_hip.h): for bodies decoded without / with a delta base
+HINT_PLAIN, HINT_DELTA = 0, 1
+
+
+class ZnHintedItem2(ctypes.Structure):
+    """struct zn_hinted_item2 of include/zipnn_hip.h"""
+    _fields_ = [("item", ZnWindowItem), ("d_hints", ctypes.c_void_p), ("hint_len", ctypes.c_size_t), ("kind", ctypes.c_int)]
+
+
+assert ctypes.sizeof(ZnHintedItem2) == 104
+
 
 class ZnCBatchItem(ctypes.Structure):
     """struct zn_cbatch_item of include/zipnn_hip.h"""
@@ -150,6 +161,14 @@ class ZnLib:
         L.zn_decompress_hinted_batch_dev.argtypes = [ctypes.POINTER(ZnHintedItem), sz, vp, ci]
         L.zn_plan_create_hinted.restype = ci
         L.zn_plan_create_hinted.argtypes = [ctypes.POINTER(ZnHintedItem), sz, vpp]
+        L.zn_hint_size_dev2.restype = ci
+        L.zn_hint_size_dev2.argtypes = [ctypes.POINTER(ZnWindowItem), ci, ctypes.POINTER(sz), vp]
+        L.zn_hint_build_dev2.restype = ci
+        L.zn_hint_build_dev2.argtypes = [ctypes.POINTER(ZnWindowItem), ci, vp, sz, vp]
+        L.zn_decompress_hinted_batch_dev2.restype = ci
+        L.zn_decompress_hinted_batch_dev2.argtypes = [ctypes.POINTER(ZnHintedItem2), sz, vp, ci]
+        L.zn_plan_create_hinted2.restype = ci
+        L.zn_plan_create_hinted2.argtypes = [ctypes.POINTER(ZnHintedItem2), sz, vpp]
         L.zn_plan_run.restype = ci
         L.zn_plan_run.argtypes = [vp, vp, ci]
         L.zn_plan_destroy.restype = ci
@@ -450,27 +469,60 @@ class ZnLib:
             arr[i].hint_len = hl
         return arr, len(items)
 
-    def hint_size_dev(self, item, stream=0):
-        """zn_hint_size_dev: bytes of the index of the whole body of `item` (a window item tuple; its window and destination are ignored)."""
+    @classmethod
+    def _hinted_items2(cls, items):
+        """items: iterable of (window item tuple, hints_ptr or None, hint_len[, kind]) -> an array of struct zn_hinted_item2 (no kind: HINT_PLAIN)."""
+        items = list(items)
+        arr = (ZnHintedItem2 * max(len(items), 1))()
+        for i, it in enumerate(items):
+            w, _ = cls._window_items([it[0]])
+            arr[i].item = w[0]
+            arr[i].d_hints = it[1] or None
+            arr[i].hint_len = it[2]
+            arr[i].kind = it[3] if len(it) > 3 else HINT_PLAIN
+        return arr, len(items)
+
+    def hint_size_dev(self, item, stream=0, kind=None):
+        """zn_hint_size_dev: bytes of the index of the whole body of `item` (a window item tuple; its window and destination are ignored).
+        kind (HINT_PLAIN / HINT_DELTA): zn_hint_size_dev2."""
         arr, _ = self._window_items([item])
         n = ctypes.c_size_t(0)
-        self._check(self._L.zn_hint_size_dev(arr, ctypes.byref(n), stream))
+        if kind is None:
+            self._check(self._L.zn_hint_size_dev(arr, ctypes.byref(n), stream))
+        else:
+            self._check(self._L.zn_hint_size_dev2(arr, kind, ctypes.byref(n), stream))
         return int(n.value)
 
-    def hint_build_dev(self, item, hints_ptr, hint_cap, stream=0):
-        """zn_hint_build_dev: build the index of the whole body of `item` into hint_cap bytes of device memory at hints_ptr (16-byte aligned)."""
+    def hint_build_dev(self, item, hints_ptr, hint_cap, stream=0, kind=None):
+        """zn_hint_build_dev: build the index of the whole body of `item` into hint_cap bytes of device memory at hints_ptr (16-byte aligned).
+        kind (HINT_PLAIN / HINT_DELTA): zn_hint_build_dev2."""
         arr, _ = self._window_items([item])
-        self._check(self._L.zn_hint_build_dev(arr, hints_ptr, hint_cap, stream))
+        if kind is None:
+            self._check(self._L.zn_hint_build_dev(arr, hints_ptr, hint_cap, stream))
+        else:
+            self._check(self._L.zn_hint_build_dev2(arr, kind, hints_ptr, hint_cap, stream))
 
     def decompress_hinted_batch_dev(self, items, stream=0, check=True):
-        """zn_decompress_hinted_batch_dev.  items: iterable of (window item tuple, hints_ptr or None, hint_len)."""
+        """zn_decompress_hinted_batch_dev.  items: iterable of (window item tuple, hints_ptr or None, hint_len) — or, with a fourth element in any of them, the
+        index's kind (HINT_PLAIN / HINT_DELTA): zn_decompress_hinted_batch_dev2."""
+        items = list(items)
+        if any(len(it) > 3 for it in items):
+            arr, n = self._hinted_items2(items)
+            self._check(self._L.zn_decompress_hinted_batch_dev2(arr, n, stream, 1 if check else 0))
+            return
         arr, n = self._hinted_items(items)
         self._check(self._L.zn_decompress_hinted_batch_dev(arr, n, stream, 1 if check else 0))
 
     def plan_create_hinted(self, items):
-        """zn_plan_create_hinted over items as for decompress_hinted_batch_dev -> a plan handle for plan_run / plan_destroy."""
-        arr, n = self._hinted_items(items)
+        """zn_plan_create_hinted (zn_plan_create_hinted2 where an item names its index's kind) over items as for decompress_hinted_batch_dev -> a plan
+        handle for plan_run / plan_destroy."""
+        items = list(items)
         h = ctypes.c_void_p(None)
+        if any(len(it) > 3 for it in items):
+            arr, n = self._hinted_items2(items)
+            self._check(self._L.zn_plan_create_hinted2(arr, n, ctypes.byref(h)))
+            return h
+        arr, n = self._hinted_items(items)
         self._check(self._L.zn_plan_create_hinted(arr, n, ctypes.byref(h)))
         return h
 

@@ -421,9 +421,9 @@ static inline void zn_window_of(const zn_window_item& it, uint64_t* n, uint64_t*
   const uint64_t end = hi == kb ? (uint64_t)it.orig_size : hi * it.chunk;
   *n = end - lo * it.chunk; *k = hi - lo;
 }
-static int hint_size_cached(const zn_window_item& it, const ZnGeom& g, size_t* bytes);
-// hints (may be null): one entry per item
-static int build_segments(const zn_window_item* items, size_t count, DecodeSet& D, const ZnHintSeg* hints = nullptr) {
+static int hint_size_cached(const zn_window_item& it, const ZnGeom& g, int kind, size_t* bytes);
+// hints (may be null): one entry per item; kinds (may be null: every index is ZN_HINT_PLAIN): the kind of each
+static int build_segments(const zn_window_item* items, size_t count, DecodeSet& D, const ZnHintSeg* hints = nullptr, const int* kinds = nullptr) {
   if (count && !items) return ZN_E_ARG;
   std::vector<ZnSeg>* segs = D.segs;
   uint64_t* pk_of = D.pk_of; uint64_t* k_of = D.k_of; uint64_t* wg_of = D.wg_of; uint64_t* tail_of = D.tail_of;
@@ -456,14 +456,17 @@ static int build_segments(const zn_window_item* items, size_t count, DecodeSet& 
     if (it.chunk_lo > it.chunk_hi || it.chunk_hi > sg.g.K) return ZN_E_ARG;
     ZnHintSeg hseg = {nullptr, 0};
     if (hints) {
-      // an index is a pointer AND a length, 16-byte aligned, at least as long as zn_hint_size_dev says for this body
+      const int kind = kinds ? kinds[i] : ZN_HINT_PLAIN;
+      if (kind != ZN_HINT_PLAIN && kind != ZN_HINT_DELTA) return ZN_E_ARG;
+      // an index is a pointer AND a length, 16-byte aligned, at least as long as zn_hint_size_dev2 says for this body and kind
       if ((hints[i].hints == nullptr) != (hints[i].len == 0) || (((uintptr_t)hints[i].hints) & 15u) != 0) return ZN_E_ARG;
       if (hints[i].hints && it.d_body && it.body_len >= 9u * (size_t)sg.g.P * sg.g.K) {
         size_t need = 0;
-        rc = hint_size_cached(it, sg.g, &need);
+        rc = hint_size_cached(it, sg.g, kind, &need);
         if (rc) return rc;
         if (hints[i].len < need) return ZN_E_ARG;
-        if (!it.d_delta) hseg = hints[i];        // (a tensor with a delta base decodes without: the delta instances read no hints)
+        // (an item reads the index of ITS instances: a tensor with a delta base a DELTA index, one without a PLAIN index; any other pairing decodes without)
+        if ((kind == ZN_HINT_DELTA) == (it.d_delta != nullptr)) hseg = hints[i];
       }
     }
     sg.kb = (uint32_t)sg.g.K; sg.c_lo = (uint32_t)it.chunk_lo;                                        // (check_geom: P·K < 2^31)
@@ -489,6 +492,12 @@ static int build_segments(const zn_window_item* items, size_t count, DecodeSet& 
     segs[q].push_back(sg);
     if (hints) { D.hsegs[q].push_back(hseg); if (hseg.hints) D.hinted[q] = true; }
   }
+  // a launch that takes a delta instance reads DELTA indexes only: its segments without a base run through that instance too, and a PLAIN index was built for
+  // the plain instance's sub-block sizes
+  for (int q = 0; q < 3; q++) if (hints && delta_of[q]) {
+    D.hinted[q] = false;
+    for (size_t i = 0; i < segs[q].size(); i++) { if (!segs[q][i].xr) D.hsegs[q][i] = ZnHintSeg{nullptr, 0}; else if (D.hsegs[q][i].hints) D.hinted[q] = true; }
+  }
   D.total_chunks = total_chunks; D.wide = wide;
   return ZN_OK;
 }
@@ -513,9 +522,10 @@ static int launch_segments(const DecodeSet& D, const ZnSeg* d_table, hipStream_t
   const size_t nseg_all = segs[0].size() + segs[1].size() + segs[2].size();
   const bool table = nseg_all > 1;
   const bool staged = table && !d_table;        // (the table goes through the pinned staging buffer)
-  // hinted launches: per plane count, when some segment has an index, none has a delta base and the wide kernel does not go first
+  // hinted launches: per plane count, when some segment has an index its launch reads (build_segments: PLAIN indexes in a launch without delta
+  // bases, DELTA indexes in one with) and the wide kernel does not go first
   bool use_h[3]; bool any_h = false;
-  for (int q = 0; q < 3; q++) { use_h[q] = D.hinted[q] && !wide && !delta_of[q] && D.hsegs[q].size() == segs[q].size() && !(table && d_table && !d_htable); any_h = any_h || use_h[q]; }
+  for (int q = 0; q < 3; q++) { use_h[q] = D.hinted[q] && !wide && D.hsegs[q].size() == segs[q].size() && !(table && d_table && !d_htable); any_h = any_h || use_h[q]; }
   const size_t seg_units = nseg_all + (any_h ? (nseg_all * sizeof(ZnHintSeg) + sizeof(ZnSeg) - 1u) / sizeof(ZnSeg) : 0u);      // staging: the ZnHintSeg table behind the segments
   if ((rc = ws_reserve(w, WS_META_C, all_pk * sizeof(ZnPlaneDesc)))) return rc;
   if ((rc = ws_reserve(w, WS_META_B, all_k))) return rc;                     // per-chunk "done by the fused kernel" flags
@@ -604,10 +614,11 @@ static int launch_segments(const DecodeSet& D, const ZnSeg* d_table, hipStream_t
     //  From about 6 GiB on the percent outweighs the 33 µs: the Llama-3-8B batch — 16 GB of bf16, its 8 KB norm vectors the partial chunks — 12.12 ms against 11.94)
     if (total_chunks > ZN_REST_MAX_CHUNKS && (tail_of[q] == 0 || k_of[q] > ZN_REST_TAIL_MAX_CHUNKS)) rest_ok[q] = false;
     if (use_h[q]) {
-      // (the plain instance's place: tail workgroups at the front, the generic launches behind it)
+      // (the plain instance's place — or, with delta bases, the delta instances': tail workgroups at the front, the generic launches behind it)
       const ZnHintSeg* d_hsegs = table ? (d_table ? d_htable : (const ZnHintSeg*)((const ZnSeg*)w.buf[WS_SEGS] + nseg_all)) + seg_base : nullptr;
-      zn_launch_decode_hinted(P, 1, segs[q][0], d_segs, nseg, D.hsegs[q][0], d_hsegs, (uint32_t)wg_of[q], d_done, d_pdone, d_status, (uint32_t)tail_of[q], d_tails, d_tail_done, stream);
-      zn_launch_decode_generic(P, segs[q][0], d_segs, nseg, pk_of[q], k_of[q], d_descs, d_status, d_done, d_pdone, d_tails, d_tail_done, stream);
+      zn_launch_decode_hinted(P, 1, segs[q][0], d_segs, nseg, D.hsegs[q][0], d_hsegs, (uint32_t)wg_of[q], d_done, d_pdone, d_status, (uint32_t)tail_of[q], d_tails, d_tail_done, stream,
+                              delta_of[q], D.inplace_of[q]);
+      zn_launch_decode_generic(P, segs[q][0], d_segs, nseg, pk_of[q], k_of[q], d_descs, d_status, d_done, d_pdone, d_tails, d_tail_done, stream, delta_of[q] && D.inplace_rot_of[q]);
       status_zeroed = true;
       continue;
     }
@@ -647,7 +658,7 @@ static int launch_segments(const DecodeSet& D, const ZnSeg* d_table, hipStream_t
 // ---- decode hints ----
 // The sizing pass over one whole body: *bytes = the length of its index (offset table + hint bytes); d_offs (may be null) receives the table.  One launch and
 // one 8-byte read-back; takes the device's workspace lock.
-static int hint_size_run(const zn_window_item& it, const ZnGeom& g, uint32_t* d_offs, size_t* bytes, hipStream_t stream) {
+static int hint_size_run(const zn_window_item& it, const ZnGeom& g, int kind, uint32_t* d_offs, size_t* bytes, hipStream_t stream) {
   int dev = 0;
   ZN_HIP(hipGetDevice(&dev));
   if (dev < 0 || dev >= 64) return ZN_E_ARG;
@@ -657,7 +668,7 @@ static int hint_size_run(const zn_window_item& it, const ZnGeom& g, uint32_t* d_
   if ((rc = ws_reserve(w, WS_TOTALS, 64))) return rc;
   if ((rc = ws_host_words(w))) return rc;
   if ((rc = ws_acquire(w, stream))) return rc;
-  zn_launch_hint_size(g, (const uint8_t*)it.d_body, it.body_len, d_offs, (uint64_t*)w.buf[WS_TOTALS], stream);
+  zn_launch_hint_size(g, (const uint8_t*)it.d_body, it.body_len, d_offs, (uint64_t*)w.buf[WS_TOTALS], stream, kind);
   { const hipError_t el = hipGetLastError(); if (el != hipSuccess) { t_hip_err = std::string("kernel launch: ") + hipGetErrorString(el); (void)ws_release(w, stream); return ZN_E_HIP; } }
   ZN_HIP(hipMemcpyAsync(w.h_total, w.buf[WS_TOTALS], sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
   if ((rc = ws_release(w, stream))) return rc;
@@ -670,23 +681,23 @@ static int hint_size_run(const zn_window_item& it, const ZnGeom& g, uint32_t* d_
 // What the hinted entry points hold a caller's hint_len against: the sizes zn_hint_size_dev / zn_hint_build_dev have worked out, remembered per body (address,
 // length, geometry); a body they have not seen is sized on the spot (a read-back: once per body).  Only an argument check — the kernels hold every read of an
 // index against the length they are given, whatever this says.
-struct HintKey { const void* body; size_t body_len, n, chunk; int P; bool operator==(const HintKey& o) const { return body == o.body && body_len == o.body_len && n == o.n && chunk == o.chunk && P == o.P; } };
-struct HintKeyHash { size_t operator()(const HintKey& k) const { return std::hash<const void*>()(k.body) ^ (k.body_len * 0x9E3779B97F4A7C15ull) ^ (k.n << 1) ^ (size_t)k.P; } };
+struct HintKey { const void* body; size_t body_len, n, chunk; int P, kind; bool operator==(const HintKey& o) const { return body == o.body && body_len == o.body_len && n == o.n && chunk == o.chunk && P == o.P && kind == o.kind; } };
+struct HintKeyHash { size_t operator()(const HintKey& k) const { return std::hash<const void*>()(k.body) ^ (k.body_len * 0x9E3779B97F4A7C15ull) ^ (k.n << 1) ^ (size_t)k.P ^ ((size_t)k.kind << 8); } };
 static std::mutex g_hint_mu;
 static std::unordered_map<HintKey, size_t, HintKeyHash> g_hint_sizes;
-static void hint_size_remember(const zn_window_item& it, const ZnGeom& g, size_t bytes) {
+static void hint_size_remember(const zn_window_item& it, const ZnGeom& g, int kind, size_t bytes) {
   std::lock_guard<std::mutex> lk(g_hint_mu);
   if (g_hint_sizes.size() > (1u << 20)) g_hint_sizes.clear();
-  g_hint_sizes[HintKey{it.d_body, it.body_len, it.orig_size, it.chunk, (int)g.P}] = bytes;
+  g_hint_sizes[HintKey{it.d_body, it.body_len, it.orig_size, it.chunk, (int)g.P, kind}] = bytes;
 }
-static int hint_size_cached(const zn_window_item& it, const ZnGeom& g, size_t* bytes) {
+static int hint_size_cached(const zn_window_item& it, const ZnGeom& g, int kind, size_t* bytes) {
   {
     std::lock_guard<std::mutex> lk(g_hint_mu);
-    auto f = g_hint_sizes.find(HintKey{it.d_body, it.body_len, it.orig_size, it.chunk, (int)g.P});
+    auto f = g_hint_sizes.find(HintKey{it.d_body, it.body_len, it.orig_size, it.chunk, (int)g.P, kind});
     if (f != g_hint_sizes.end()) { *bytes = f->second; return ZN_OK; }
   }
-  const int rc = hint_size_run(it, g, nullptr, bytes, nullptr);
-  if (rc == ZN_OK) hint_size_remember(it, g, *bytes);
+  const int rc = hint_size_run(it, g, kind, nullptr, bytes, nullptr);
+  if (rc == ZN_OK) hint_size_remember(it, g, kind, *bytes);
   return rc;
 }
 static int hint_item_geom(const zn_window_item* it, ZnGeom* g) {
@@ -697,21 +708,25 @@ static int hint_item_geom(const zn_window_item* it, ZnGeom* g) {
   return ZN_OK;
 }
 
-int zn_hint_size_dev(const zn_window_item* item, size_t* hint_bytes, void* stream_) {
+int zn_hint_size_dev(const zn_window_item* item, size_t* hint_bytes, void* stream_) { return zn_hint_size_dev2(item, ZN_HINT_PLAIN, hint_bytes, stream_); }
+int zn_hint_size_dev2(const zn_window_item* item, int kind, size_t* hint_bytes, void* stream_) {
   if (!hint_bytes) return ZN_E_ARG;
   *hint_bytes = 0;
+  if (kind != ZN_HINT_PLAIN && kind != ZN_HINT_DELTA) return ZN_E_ARG;
   try {
     ZnGeom g;
     int rc = hint_item_geom(item, &g);
     if (rc) return rc;
     t_kernels.clear();
-    rc = hint_size_run(*item, g, nullptr, hint_bytes, (hipStream_t)stream_);
-    if (rc == ZN_OK) hint_size_remember(*item, g, *hint_bytes);
+    rc = hint_size_run(*item, g, kind, nullptr, hint_bytes, (hipStream_t)stream_);
+    if (rc == ZN_OK) hint_size_remember(*item, g, kind, *hint_bytes);
     return rc;
   } catch (...) { return ZN_E_ALLOC; }
 }
 
-int zn_hint_build_dev(const zn_window_item* item, void* d_hints, size_t hint_cap, void* stream_) {
+int zn_hint_build_dev(const zn_window_item* item, void* d_hints, size_t hint_cap, void* stream_) { return zn_hint_build_dev2(item, ZN_HINT_PLAIN, d_hints, hint_cap, stream_); }
+int zn_hint_build_dev2(const zn_window_item* item, int kind, void* d_hints, size_t hint_cap, void* stream_) {
+  if (kind != ZN_HINT_PLAIN && kind != ZN_HINT_DELTA) return ZN_E_ARG;
   try {
     ZnGeom g;
     int rc = hint_item_geom(item, &g);
@@ -721,9 +736,9 @@ int zn_hint_build_dev(const zn_window_item* item, void* d_hints, size_t hint_cap
     t_kernels.clear();
     // the table first (it is the head of the buffer: what fits the smallest legal capacity), and with it the size the bytes need
     size_t need = 0;
-    rc = hint_size_run(*item, g, (uint32_t*)d_hints, &need, stream);
+    rc = hint_size_run(*item, g, kind, (uint32_t*)d_hints, &need, stream);
     if (rc) return rc;
-    hint_size_remember(*item, g, need);
+    hint_size_remember(*item, g, kind, need);
     if (hint_cap < need) return ZN_E_ARG;
     if (g.K == 0) return ZN_OK;
     int dev = 0;
@@ -746,7 +761,8 @@ int zn_hint_build_dev(const zn_window_item* item, void* d_hints, size_t hint_cap
     uint32_t* d_status = (uint32_t*)w.buf[WS_WORDS];
     ZN_HIP(hipMemsetAsync(d_status, 0, 4 * sizeof(uint32_t), stream));
     const ZnHintSeg hs = {(uint8_t*)d_hints, (uint64_t)need};
-    zn_launch_decode_hinted((int)g.P, 2, sg, nullptr, 1, hs, nullptr, (uint32_t)((g.K + sg.ncg - 1u) / sg.ncg), (uint8_t*)w.buf[WS_META_B], (uint8_t*)w.buf[WS_ENC], d_status, 0, nullptr, nullptr, stream);
+    zn_launch_decode_hinted((int)g.P, 2, sg, nullptr, 1, hs, nullptr, (uint32_t)((g.K + sg.ncg - 1u) / sg.ncg), (uint8_t*)w.buf[WS_META_B], (uint8_t*)w.buf[WS_ENC], d_status, 0, nullptr, nullptr, stream,
+                            kind == ZN_HINT_DELTA, false);      // (DELTA: built by the delta instance — no base, no rows —, whose sub-block sizes the delta decodes choose)
     { const hipError_t el = hipGetLastError(); if (el != hipSuccess) { t_hip_err = std::string("kernel launch: ") + hipGetErrorString(el); (void)ws_release(w, stream); return ZN_E_HIP; } }
     if ((rc = ws_release(w, stream))) return rc;
     ZN_HIP(hipStreamSynchronize(stream));
@@ -760,6 +776,12 @@ static int split_hinted(const zn_hinted_item* items, size_t count, std::vector<z
   for (size_t i = 0; i < count; i++) { win[i] = items[i].item; hs[i].hints = (uint8_t*)items[i].d_hints; hs[i].len = items[i].hint_len; }
   return ZN_OK;
 }
+static int split_hinted2(const zn_hinted_item2* items, size_t count, std::vector<zn_window_item>& win, std::vector<ZnHintSeg>& hs, std::vector<int>& kinds) {
+  if (count && !items) return ZN_E_ARG;
+  win.resize(count); hs.resize(count); kinds.resize(count);
+  for (size_t i = 0; i < count; i++) { win[i] = items[i].item; hs[i].hints = (uint8_t*)items[i].d_hints; hs[i].len = items[i].hint_len; kinds[i] = items[i].kind; }
+  return ZN_OK;
+}
 int zn_decompress_hinted_batch_dev(const zn_hinted_item* items, size_t count, void* stream_, int check) {
   try {
     std::vector<zn_window_item> win; std::vector<ZnHintSeg> hs;
@@ -767,6 +789,16 @@ int zn_decompress_hinted_batch_dev(const zn_hinted_item* items, size_t count, vo
     if (rc) return rc;
     DecodeSet D;
     rc = build_segments(win.data(), count, D, hs.data());
+    return rc ? rc : launch_segments(D, nullptr, (hipStream_t)stream_, check);
+  } catch (...) { return ZN_E_ALLOC; }
+}
+int zn_decompress_hinted_batch_dev2(const zn_hinted_item2* items, size_t count, void* stream_, int check) {
+  try {
+    std::vector<zn_window_item> win; std::vector<ZnHintSeg> hs; std::vector<int> kinds;
+    int rc = split_hinted2(items, count, win, hs, kinds);
+    if (rc) return rc;
+    DecodeSet D;
+    rc = build_segments(win.data(), count, D, hs.data(), kinds.data());
     return rc ? rc : launch_segments(D, nullptr, (hipStream_t)stream_, check);
   } catch (...) { return ZN_E_ALLOC; }
 }
@@ -882,7 +914,7 @@ struct zn_plan {
 };
 extern "C" {
 
-static int plan_create(const zn_window_item* items, size_t count, const ZnHintSeg* hints, zn_plan** plan);
+static int plan_create(const zn_window_item* items, size_t count, const ZnHintSeg* hints, zn_plan** plan, const int* kinds = nullptr);
 int zn_plan_create(const zn_window_item* items, size_t count, zn_plan** plan) { return plan_create(items, count, nullptr, plan); }
 int zn_plan_create_hinted(const zn_hinted_item* items, size_t count, zn_plan** plan) {
   if (!plan) return ZN_E_ARG;
@@ -893,7 +925,16 @@ int zn_plan_create_hinted(const zn_hinted_item* items, size_t count, zn_plan** p
     return rc ? rc : plan_create(win.data(), count, hs.data(), plan);
   } catch (...) { return ZN_E_ALLOC; }
 }
-static int plan_create(const zn_window_item* items, size_t count, const ZnHintSeg* hints, zn_plan** plan) {
+int zn_plan_create_hinted2(const zn_hinted_item2* items, size_t count, zn_plan** plan) {
+  if (!plan) return ZN_E_ARG;
+  *plan = nullptr;
+  try {
+    std::vector<zn_window_item> win; std::vector<ZnHintSeg> hs; std::vector<int> kinds;
+    const int rc = split_hinted2(items, count, win, hs, kinds);
+    return rc ? rc : plan_create(win.data(), count, hs.data(), plan, kinds.data());
+  } catch (...) { return ZN_E_ALLOC; }
+}
+static int plan_create(const zn_window_item* items, size_t count, const ZnHintSeg* hints, zn_plan** plan, const int* kinds) {
   if (!plan) return ZN_E_ARG;
   *plan = nullptr;
   try {
@@ -902,7 +943,7 @@ static int plan_create(const zn_window_item* items, size_t count, const ZnHintSe
     if (dev < 0 || dev >= 64) return ZN_E_ARG;
     std::unique_ptr<zn_plan> pl(new zn_plan());          // (whatever throws or fails below takes the plan, its table and its event with it)
     pl->dev = dev;
-    const int rc = build_segments(items, count, pl->D, hints);
+    const int rc = build_segments(items, count, pl->D, hints, kinds);
     if (rc) return rc;
     std::vector<ZnSeg> all;
     for (int q = 0; q < 3; q++) all.insert(all.end(), pl->D.segs[q].begin(), pl->D.segs[q].end());

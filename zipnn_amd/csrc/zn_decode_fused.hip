@@ -876,9 +876,53 @@ ZN_TU_LOCAL __device__ void zn_decode_tail_wg(ZnFusedLds& L_, const ZnSeg& one, 
 // as the base.  The tree description is parsed by wave 0 between the passes.  Returns 1 = ok, 0 = a stream did not
 // decode cleanly, -1 = a plane this kernel does not take (the generic path redoes the chunk).
 // (Inlined: as a real call it halved the speed of the common one-plane case — measured, profiles/README.md.)
-template <int P>
+// In the hinted unit (zn_decode_hinted.hip, see zn_k_decode_fused below) the function has the hint mode HM as a template parameter and three more arguments — the
+// segment's index, the body's chunk count and the table entry of (this chunk, plane 0) —: a pass of plane p2 looks its region up at entry + p2, as the kernel
+// does for the first plane, and hands it to the wave function (HM 1 reads, HM 2 writes; an empty region: that pass runs without).  An index of kind ZN_HINT_DELTA
+// has such regions; here HM is the constant 0 and the macros below expand to nothing.
+#if defined(ZN_DECODE_HINTED_TU)
+#define ZN_K_DECODE_NAME zn_k_decode_hinted
+#define ZN_K_HM_TPARAM , int HM
+#define ZN_K_HM_PARAMS , ZnHintSeg one_h, const ZnHintSeg* __restrict__ hsegs
+#define ZN_K_HM_CONST
+#define ZN_K_HM_MP_PARAMS , ZnHintSeg hseg_, uint32_t hkb_, uint64_t hent0_
+#define ZN_K_HM_MP_TARG , HM
+#define ZN_K_HM_MP_XQ (HM == 2 ? (const uint8_t*)nullptr : (const uint8_t*)outq)      // (a build has no rows: nothing to accumulate into)
+#define ZN_K_HM_MP_HINT_ARGS , hq2, hcap2
+// (the kernel's call: only the delta instances pass their hint mode on — further planes of PLAIN bodies decode without hints, as their instances always have)
+#define ZN_K_HM_MP_CALL_TARG , (X ? HM : 0)
+#define ZN_K_HM_MP_CALL_ARGS , (X ? (hsegs != nullptr ? hsegs[seg_i] : one_h) : ZnHintSeg{nullptr, 0}), (X ? zn_uniform(S_.kb) : 0u), (X ? ((uint64_t)zn_uniform(S_.c_lo) + c) * (uint32_t)P : 0ull)
+// (the region of (chunk, plane p2), looked up and checked against the buffer's length exactly as the first plane's is in the kernel)
+#define ZN_K_HM_MP_REGION \
+    uint8_t* hq2 = nullptr; uint32_t hcap2 = 0; \
+    if constexpr (HM != 0) { \
+      const uint32_t b1 = zn_hint_stream_bytes(l1, seg, UNIT), b2 = zn_hint_stream_bytes(l2, seg, UNIT), b3 = zn_hint_stream_bytes(l3, seg, UNIT), b4 = zn_hint_stream_bytes(l4, seg, UNIT); \
+      const uint32_t h_before = (wave > 0 ? b1 : 0u) + (wave > 1 ? b2 : 0u) + (wave > 2 ? b3 : 0u), h_mine = (wave == 0) ? b1 : (wave == 1) ? b2 : (wave == 2) ? b3 : b4; \
+      uint8_t* const hbuf = zn_uniform_ptr(hseg_.hints); const uint64_t hlen = zn_uniform64(hseg_.len); \
+      const uint64_t kb_ = zn_uniform(hkb_), ent = zn_uniform64(hent0_) + (uint32_t)p2; \
+      const uint64_t hdr = zn_hint_header_bytes(kb_ * (uint32_t)P); \
+      if (hbuf != nullptr && hlen >= hdr && ent < kb_ * (uint32_t)P) { \
+        const uint32_t* offs = (const uint32_t*)hbuf; \
+        const uint32_t o0 = zn_uniform(offs[ent]), o1 = zn_uniform(offs[ent + 1u]); \
+        if (o0 >= hdr && o1 >= o0 && (uint64_t)o1 <= hlen && (uint64_t)h_before + h_mine <= (uint64_t)(o1 - o0)) { hq2 = hbuf + o0 + h_before; hcap2 = h_mine; } \
+      } \
+    }
+#else
+#define ZN_K_DECODE_NAME zn_k_decode_fused
+#define ZN_K_HM_TPARAM
+#define ZN_K_HM_PARAMS
+#define ZN_K_HM_CONST constexpr int HM = 0; const ZnHintSeg one_h = {nullptr, 0}; const ZnHintSeg* const hsegs = nullptr; (void)one_h; (void)hsegs;
+#define ZN_K_HM_MP_PARAMS
+#define ZN_K_HM_MP_TARG
+#define ZN_K_HM_MP_XQ outq
+#define ZN_K_HM_MP_HINT_ARGS
+#define ZN_K_HM_MP_CALL_TARG
+#define ZN_K_HM_MP_CALL_ARGS
+#define ZN_K_HM_MP_REGION
+#endif
+template <int P ZN_K_HM_TPARAM>
 __device__ __forceinline__ int zn_fused_more_passes(ZnFusedLds& L, const ZnGeom& g, const uint8_t* __restrict__ body, const uint8_t* body_end,
-                                                    uint8_t* outq, uint32_t j, uint32_t more, uint32_t seg ZN_PT_PARAM) {
+                                                    uint8_t* outq, uint32_t j, uint32_t more, uint32_t seg ZN_PT_PARAM ZN_K_HM_MP_PARAMS) {
   constexpr int EPL = (P == 1) ? 16 : 8;
   constexpr uint32_t UNIT = 64u * EPL;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));   // (wave-uniform, and the compiler should know: everything derived from it lives in scalar registers)
@@ -914,11 +958,12 @@ __device__ __forceinline__ int zn_fused_more_passes(ZnFusedLds& L, const ZnGeom&
     uint32_t Du2 = ((ZN_F_RING_BYTES - UNIT - 128u) * slen2) / (256u * seg);
     Du2 = Du2 > ZN_F_DMAX ? ZN_F_DMAX : (Du2 < 1u ? 1u : Du2);
     Du2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)Du2);
-#define ZN_ACC_ARGS g, body, body_end, outq, outq, pl2, rawq, L.lut, ring, in, lane, seg, TL2, Du2, stream2, slen2, false ZN_PT_PASS
+    ZN_K_HM_MP_REGION
+#define ZN_ACC_ARGS g, body, body_end, outq, ZN_K_HM_MP_XQ, pl2, rawq, L.lut, ring, in, lane, seg, TL2, Du2, stream2, slen2, false ZN_PT_PASS ZN_K_HM_MP_HINT_ARGS
     bool ok2;
-    if (p2 == 1) ok2 = zn_fused_wave<P, (P >= 2 ? 1 : 0), 0, true>(ZN_ACC_ARGS);
-    else if (p2 == 2) ok2 = zn_fused_wave<P, (P >= 4 ? 2 : 0), 0, true>(ZN_ACC_ARGS);
-    else ok2 = zn_fused_wave<P, (P >= 4 ? 3 : 0), 0, true>(ZN_ACC_ARGS);
+    if (p2 == 1) ok2 = zn_fused_wave<P, (P >= 2 ? 1 : 0), 0, true ZN_K_HM_MP_TARG>(ZN_ACC_ARGS);
+    else if (p2 == 2) ok2 = zn_fused_wave<P, (P >= 4 ? 2 : 0), 0, true ZN_K_HM_MP_TARG>(ZN_ACC_ARGS);
+    else ok2 = zn_fused_wave<P, (P >= 4 ? 3 : 0), 0, true ZN_K_HM_MP_TARG>(ZN_ACC_ARGS);
 #undef ZN_ACC_ARGS
     ok = ok && ok2;
   }
@@ -938,20 +983,10 @@ static_assert(sizeof(ZnFusedLds) * ZN_F_WAVES_PER_SIMD <= 160u * 1024u, "ZnFused
 // return at once in nearly every call; `descs_rest` = the launch's plane descriptors (the generic kernels' workspace).
 // The HINTED kernels are this kernel's text under another name: zn_decode_hinted.hip compiles this file with ZN_DECODE_HINTED_TU set, and the
 // definition below is then zn_k_decode_hinted<P, X, REST, HM> — launched as <P, false, false, HM>: the plain instance, what it does not take is left to the generic
-// launches behind it — with two more arguments: the index of segment i is entry i of `hsegs`, a table parallel to `segs` (`one_h` beside `one`).  HM 1: its stream
-// decoders read the index (a segment without one, hints == null, decodes exactly as here); HM 2: they write it — launched without tail workgroups, and nothing but
-// hint bytes and the done flags is stored.  In this unit HM is the constant 0 and the kernel is, token for token, what it was before there were hints.
-#if defined(ZN_DECODE_HINTED_TU)
-#define ZN_K_DECODE_NAME zn_k_decode_hinted
-#define ZN_K_HM_TPARAM , int HM
-#define ZN_K_HM_PARAMS , ZnHintSeg one_h, const ZnHintSeg* __restrict__ hsegs
-#define ZN_K_HM_CONST
-#else
-#define ZN_K_DECODE_NAME zn_k_decode_fused
-#define ZN_K_HM_TPARAM
-#define ZN_K_HM_PARAMS
-#define ZN_K_HM_CONST constexpr int HM = 0; const ZnHintSeg one_h = {nullptr, 0}; const ZnHintSeg* const hsegs = nullptr; (void)one_h; (void)hsegs;
-#endif
+// launches behind it, or as <P, true, REST, HM>: the delta instances, for indexes of kind ZN_HINT_DELTA (§3.6) — with two more arguments: the index of segment i is
+// entry i of `hsegs`, a table parallel to `segs` (`one_h` beside `one`).  HM 1: its stream decoders read the index (a segment without one, hints == null, decodes
+// exactly as here); HM 2: they write it — launched without tail workgroups, and nothing but hint bytes and the done flags is stored.  In this unit HM is the
+// constant 0 and the kernel is, token for token, what it was before there were hints (the ZN_K_HM_* macros are defined ahead of zn_fused_more_passes).
 template <int P, bool X, bool REST = false ZN_K_HM_TPARAM>
 __global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void ZN_K_DECODE_NAME(ZnSeg one, const ZnSeg* __restrict__ segs, uint32_t nseg,
                                                                   uint8_t* __restrict__ done_all, uint8_t* __restrict__ pdone_all,
@@ -1165,8 +1200,10 @@ __global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void ZN_K_DECODE
 #undef ZN_WAVE_ARGS
 #undef ZN_HINT_ARGS
     // ---- further Huffman planes (deltas, sparse tensors: every plane compresses): one more pass per plane
-    if (HM != 2 && P >= 2 && __builtin_expect(more != 0u, 0)) {      // (further planes are decoded without hints; an index build has no rows to add them to)
-      const int r2 = zn_fused_more_passes<P>(L, g, body, body_end, outq, j, more, seg ZN_PT_PASS);
+    // (the plain instances decode further planes without hints, and their index build has no rows to add them to; the DELTA instances of the hinted unit hand
+    //  every pass its own region — re-derived here on every run of the passes, the undo's second run included — and their build runs the passes to write them)
+    if ((HM != 2 || X) && P >= 2 && __builtin_expect(more != 0u, 0)) {
+      const int r2 = zn_fused_more_passes<P ZN_K_HM_MP_CALL_TARG>(L, g, body, body_end, outq, j, more, seg ZN_PT_PASS ZN_K_HM_MP_CALL_ARGS);
       // (IN PLACE, xq == outq, the rows of this chunk no longer hold the base the generic path needs: they hold it XORed with the first pass and with the passes
       //  of the planes ahead of the one given up.  Every one of those passes is a function of the body alone and XORs into what stands there — the same
       //  passes once more, up to the same refusal, and the rows hold the base again.  The tables of the first plane are parsed again: the later passes overwrote them.)
@@ -1193,12 +1230,14 @@ __global__ __launch_bounds__(ZN_F_THREADS, ZN_F_WAVES_PER_SIMD) void ZN_K_DECODE
   ZN_PT_FLUSH();
 }
 
-// The sizing pass of an index: one workgroup walks the body's type and size tables, 256 chunks at a time, and gives the FIRST Huffman-coded plane of every full
+// The sizing pass of an index: one workgroup walks the body's type and size tables, 256 chunks at a time, and gives the Huffman-coded planes of every full
 // chunk the fused kernel would take a region of zn_hint_stream_bytes per huff0 stream (the jump table stands behind a tree description whose length is its first
-// byte's to say).  offs (may be null: size only) gets one 32-bit offset per (chunk, plane) — entry c P + p, from the start of the buffer, whose head the table
-// itself is — and the total as its last entry; *total the same in 64 bits (a total that does not fit 32 bits is refused by the host).
+// byte's to say) — kind ZN_HINT_PLAIN (0): the FIRST such plane alone; ZN_HINT_DELTA (1): every one of them, the further planes' regions behind the first's in
+// plane order.  offs (may be null: size only) gets one 32-bit offset per (chunk, plane) — entry c P + p, from the start of the buffer, whose head the table
+// itself is: the chunk's start plus the regions of the planes ahead of p, so that a plane without a region has an empty one — and the total as its last entry;
+// *total the same in 64 bits (a total that does not fit 32 bits is refused by the host).
 #if defined(ZN_DECODE_HINTED_TU)
-__global__ __launch_bounds__(256) void zn_k_hint_size(ZnGeom g, const uint8_t* __restrict__ body, uint64_t body_len, uint32_t* __restrict__ offs, uint64_t* __restrict__ total) {
+__global__ __launch_bounds__(256) void zn_k_hint_size(ZnGeom g, const uint8_t* __restrict__ body, uint64_t body_len, uint32_t* __restrict__ offs, uint64_t* __restrict__ total, uint32_t kind) {
   __shared__ uint32_t sh[256];
   __shared__ uint64_t run;
   const uint32_t tid = threadIdx.x, P = g.P;
@@ -1210,34 +1249,36 @@ __global__ __launch_bounds__(256) void zn_k_hint_size(ZnGeom g, const uint8_t* _
   __syncthreads();
   for (uint64_t base = 0; base < g.K; base += 256u) {
     const uint64_t c = base + tid;
-    uint32_t sz = 0; int h = -1;
+    uint32_t sz = 0; uint32_t szp[4] = {0u, 0u, 0u, 0u};      // the chunk's hint bytes / those of its plane p
     if (c < g.K && geom_ok && zn_chunk_len(g, c) == g.chunk) {
-      bool elig = true; ZnPcMeta mh; mh.off = 0; mh.csize = 0;
+      bool elig = true; int h = -1; ZnPcMeta mh[4]; bool huf[4] = {false, false, false, false};
       for (uint32_t p = 0; p < P; p++) {
         const ZnPcMeta m = zn_pc_meta(g, (uint32_t)g.K, 0u, body, body_len, p, c);
-        uint32_t kind = 99u;
+        uint32_t pk = 99u;
         if (m.ok && m.type <= 1u) {
-          if (m.type == 0u) { if (m.csize >= plen) kind = ZN_KIND_RAW; }
-          else if (m.csize == plen) kind = ZN_KIND_RAW;
-          else if (m.csize == 1u) kind = ZN_KIND_RLE;
-          else if (m.csize > 1u && m.csize < plen) kind = ZN_KIND_HUF;
+          if (m.type == 0u) { if (m.csize >= plen) pk = ZN_KIND_RAW; }
+          else if (m.csize == plen) pk = ZN_KIND_RAW;
+          else if (m.csize == 1u) pk = ZN_KIND_RLE;
+          else if (m.csize > 1u && m.csize < plen) pk = ZN_KIND_HUF;
         }
-        if (kind == 99u) elig = false;
-        if (kind == ZN_KIND_HUF && h < 0) { h = (int)p; mh = m; }
+        if (pk == 99u) elig = false;
+        mh[p] = m;
+        if (pk == ZN_KIND_HUF) { if (h < 0) { h = (int)p; huf[p] = true; } else if (kind != 0u) huf[p] = true; }
       }
-      if (elig && h >= 0 && body + mh.off + mh.csize <= body_end) {
-        const uint8_t* src = body + mh.off;
+      for (uint32_t p = 0; p < P; p++) if (elig && huf[p] && body + mh[p].off + mh[p].csize <= body_end) {
+        const uint8_t* src = body + mh[p].off;
         const uint32_t h0 = src[0];
         const uint32_t hs = 1u + (h0 >= 128u ? (h0 - 127u + 1u) / 2u : h0);
-        if (hs < mh.csize && mh.csize - hs >= 10u) {
-          const uint8_t* js = src + hs; const uint32_t rem = mh.csize - hs;
+        if (hs < mh[p].csize && mh[p].csize - hs >= 10u) {
+          const uint8_t* js = src + hs; const uint32_t rem = mh[p].csize - hs;
           const uint32_t l1 = zn_ld16(js), l2 = zn_ld16(js + 2), l3 = zn_ld16(js + 4);
           if (l1 && l2 && l3 && l1 + l2 + l3 + 6u < rem) {
             const uint32_t l4 = rem - 6u - l1 - l2 - l3;
-            sz = zn_hint_stream_bytes(l1, seg, unit) + zn_hint_stream_bytes(l2, seg, unit) + zn_hint_stream_bytes(l3, seg, unit) + zn_hint_stream_bytes(l4, seg, unit);
+            szp[p] = zn_hint_stream_bytes(l1, seg, unit) + zn_hint_stream_bytes(l2, seg, unit) + zn_hint_stream_bytes(l3, seg, unit) + zn_hint_stream_bytes(l4, seg, unit);
           }
         }
       }
+      sz = szp[0] + szp[1] + szp[2] + szp[3];
     }
     // exclusive scan of the 256 sizes
     sh[tid] = sz;
@@ -1249,7 +1290,7 @@ __global__ __launch_bounds__(256) void zn_k_hint_size(ZnGeom g, const uint8_t* _
       __syncthreads();
     }
     const uint64_t start = run + (sh[tid] - sz);
-    if (offs != nullptr && c < g.K) for (uint32_t p = 0; p < P; p++) offs[c * P + p] = (uint32_t)(start + (((int)p > h && h >= 0) ? sz : 0u));
+    if (offs != nullptr && c < g.K) { uint32_t ahead = 0; for (uint32_t p = 0; p < P; p++) { offs[c * P + p] = (uint32_t)(start + ahead); ahead += szp[p]; } }
     __syncthreads();
     if (tid == 255u) run += sh[255];
     __syncthreads();
@@ -1257,19 +1298,30 @@ __global__ __launch_bounds__(256) void zn_k_hint_size(ZnGeom g, const uint8_t* _
   if (tid == 0) { if (offs != nullptr) offs[g.K * P] = (uint32_t)run; *total = run; }
 }
 
-void zn_launch_hint_size(const ZnGeom& g, const uint8_t* d_body, uint64_t body_len, uint32_t* d_offs, uint64_t* d_total, hipStream_t stream) {
-  hipLaunchKernelGGL(zn_k_hint_size, dim3(1), dim3(256), 0, stream, g, d_body, body_len, d_offs, d_total);
+void zn_launch_hint_size(const ZnGeom& g, const uint8_t* d_body, uint64_t body_len, uint32_t* d_offs, uint64_t* d_total, hipStream_t stream, int kind) {
+  hipLaunchKernelGGL(zn_k_hint_size, dim3(1), dim3(256), 0, stream, g, d_body, body_len, d_offs, d_total, (uint32_t)kind);
   zn_note_kernel("zn_k_hint_size");
 }
 void zn_launch_decode_hinted(int P, int mode, const ZnSeg& one, const ZnSeg* d_segs, uint32_t nseg, const ZnHintSeg& one_h, const ZnHintSeg* d_hsegs, uint32_t total_wg,
-                             uint8_t* d_done, uint8_t* d_pdone, uint32_t* d_status, uint32_t ntail, uint8_t* d_tail_scratch, uint8_t* d_tail_done, hipStream_t stream) {
+                             uint8_t* d_done, uint8_t* d_pdone, uint32_t* d_status, uint32_t ntail, uint8_t* d_tail_scratch, uint8_t* d_tail_done, hipStream_t stream,
+                             bool delta, bool inplace) {
   if (total_wg == 0) return;
   const uint32_t ntail_wg = (mode == 2) ? 0u : 4u * ntail;      // (four tail workgroups per plane, at the front of the grid: zn_launch_decode_fused)
-#define ZN_GOH(P_, M_) hipLaunchKernelGGL((zn_k_decode_hinted<P_, false, false, M_>), dim3(total_wg + ntail_wg), dim3(ZN_F_THREADS), 0, stream, one, d_segs, nseg, d_done, d_pdone, d_status, ntail_wg, d_tail_scratch, d_tail_done, 0u, (ZnPlaneDesc*)nullptr, total_wg, 0u, (uint32_t*)nullptr, one_h, d_hsegs)
-  if (mode == 2) { if (P == 1) ZN_GOH(1, 2); else if (P == 2) ZN_GOH(2, 2); else ZN_GOH(4, 2); }
-  else { if (P == 1) ZN_GOH(1, 1); else if (P == 2) ZN_GOH(2, 1); else ZN_GOH(4, 1); }
+#define ZN_GOH(P_, X_, R_, M_) hipLaunchKernelGGL((zn_k_decode_hinted<P_, X_, R_, M_>), dim3(total_wg + ntail_wg), dim3(ZN_F_THREADS), 0, stream, one, d_segs, nseg, d_done, d_pdone, d_status, ntail_wg, d_tail_scratch, d_tail_done, 0u, (ZnPlaneDesc*)nullptr, total_wg, 0u, (uint32_t*)nullptr, one_h, d_hsegs)
+  if (!delta) {
+    if (mode == 2) { if (P == 1) ZN_GOH(1, false, false, 2); else if (P == 2) ZN_GOH(2, false, false, 2); else ZN_GOH(4, false, false, 2); }
+    else { if (P == 1) ZN_GOH(1, false, false, 1); else if (P == 2) ZN_GOH(2, false, false, 1); else ZN_GOH(4, false, false, 1); }
+    zn_note_kernel(mode == 2 ? "zn_k_decode_hinted^build" : ntail_wg ? "zn_k_decode_hinted+tail" : "zn_k_decode_hinted");
+    return;
+  }
+  // kind ZN_HINT_DELTA: the delta instances — the same choice between them as zn_launch_decode_fused makes (in place with more than one plane: the instance that
+  // can hand the base back), and the build by the delta instance without a base, whose sub-block sizes are the ones those two choose
+  if (mode == 2) { if (P == 1) ZN_GOH(1, true, false, 2); else if (P == 2) ZN_GOH(2, true, false, 2); else ZN_GOH(4, true, false, 2); }
+  else if (inplace && P > 1) { if (P == 2) ZN_GOH(2, true, true, 1); else ZN_GOH(4, true, true, 1); }
+  else { if (P == 1) ZN_GOH(1, true, false, 1); else if (P == 2) ZN_GOH(2, true, false, 1); else ZN_GOH(4, true, false, 1); }
 #undef ZN_GOH
-  zn_note_kernel(mode == 2 ? "zn_k_decode_hinted^build" : ntail_wg ? "zn_k_decode_hinted+tail" : "zn_k_decode_hinted");
+  zn_note_kernel(mode == 2 ? "zn_k_decode_hinted^delta^build" : (inplace && P > 1) ? (ntail_wg ? "zn_k_decode_hinted^delta^inplace+tail" : "zn_k_decode_hinted^delta^inplace")
+                                                              : (ntail_wg ? "zn_k_decode_hinted^delta+tail" : "zn_k_decode_hinted^delta"));
 }
 #endif
 

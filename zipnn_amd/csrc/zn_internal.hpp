@@ -69,12 +69,17 @@ int zn_decode_use_wide(uint64_t total_full_chunks, bool delta, bool weights_like
 // the segment table (or, for a single segment, a second kernel argument beside it); hints == null: that segment decodes without.
 struct ZnHintSeg { uint8_t* hints; uint64_t len; };
 static inline uint64_t zn_hint_header_bytes_host(uint64_t pk) { return ((pk + 1u) * 4u + 63u) & ~63ull; }
+// Two kinds of index (include/zipnn_hip.h: ZN_HINT_PLAIN / ZN_HINT_DELTA), one container: a PLAIN index has a region for the first Huffman-coded plane of a chunk
+// and is written and read by the plain instance; a DELTA index has one for every Huffman-coded plane and is written and read by the delta instances, whose
+// sub-block sizes differ from the plain instance's.
 // sizing pass: d_offs null = only the total (8 bytes at d_total)
-void zn_launch_hint_size(const ZnGeom& g, const uint8_t* d_body, uint64_t body_len, uint32_t* d_offs, uint64_t* d_total, hipStream_t stream);
-// mode 1: the hinted decode of a launch without delta bases and without the wide kernel in front — in place of zn_launch_decode_fused's plain instance: the caller
-// follows it with zn_launch_decode_generic.  mode 2: the index build (one whole body, no tail workgroups, no destination).
+void zn_launch_hint_size(const ZnGeom& g, const uint8_t* d_body, uint64_t body_len, uint32_t* d_offs, uint64_t* d_total, hipStream_t stream, int kind = 0);
+// mode 1: the hinted decode of a launch without the wide kernel in front — in place of zn_launch_decode_fused's plain instance (delta false: no segment has a delta
+// base) or of its delta instances (delta true; inplace: some segment's base is its destination): the caller follows it with zn_launch_decode_generic.
+// mode 2: the index build (one whole body, no tail workgroups, no destination); delta: of kind DELTA.
 void zn_launch_decode_hinted(int P, int mode, const ZnSeg& one, const ZnSeg* d_segs, uint32_t nseg, const ZnHintSeg& one_h, const ZnHintSeg* d_hsegs, uint32_t total_wg,
-                             uint8_t* d_done, uint8_t* d_pdone, uint32_t* d_status, uint32_t ntail, uint8_t* d_tail_scratch, uint8_t* d_tail_done, hipStream_t stream);
+                             uint8_t* d_done, uint8_t* d_pdone, uint32_t* d_status, uint32_t ntail, uint8_t* d_tail_scratch, uint8_t* d_tail_done, hipStream_t stream,
+                             bool delta = false, bool inplace = false);
 
 // ---- encode ----
 struct ZnEncDesc {           // per (plane, chunk): what the emit kernel needs for a plane kept as huff0 / RLE

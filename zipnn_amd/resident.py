@@ -87,10 +87,12 @@ class _Entry:
         """-> the item tuple of ZnLib.decompress_window_batch_dev / plan_create for chunks [lo, hi) of this tensor (delta_ptr: the WHOLE tensor's base)."""
         return (self.body.data_ptr(), self.body.numel(), self.P, self.bits, self.byts, self.chunk, self.nbytes, lo, hi, dst_ptr, delta_ptr)
 
-    def hinted(self, lo, hi, dst_ptr):
-        """-> the item of ZnLib.decompress_hinted_batch_dev / plan_create_hinted: the window plus the body's index (None, 0 without one)."""
+    def hinted(self, lo, hi, dst_ptr, delta_ptr=None):
+        """-> the item of ZnLib.decompress_hinted_batch_dev / plan_create_hinted: the window plus the body's index (None, 0 without one).  With a delta
+        base the item names the index's kind as well: a delta body's index is of kind HINT_DELTA (build_index(deltas=True))."""
         h = self.hints
-        return (self.window(lo, hi, dst_ptr), h.data_ptr() if h is not None else None, h.numel() if h is not None else 0)
+        item = (self.window(lo, hi, dst_ptr, delta_ptr), h.data_ptr() if h is not None else None, h.numel() if h is not None else 0)
+        return item + (_capi.HINT_DELTA,) if delta_ptr is not None else item
 
     def view(self, flat):
         """flat uint8 bytes of the whole tensor -> the tensor."""
@@ -153,7 +155,7 @@ class ResidentCheckpoint:
     @classmethod
     def from_file(cls, path, device="cuda:0", index=False, digests=False, verify=False, base=None, verify_base=True):
         """A `.znn.safetensors` file (this library's or the reference's): its data section goes to `device` once, in one transfer, and stays.
-        index=True: build_index() on the new store.
+        index=True: build_index() on the new store; index="deltas": build_index(deltas=True) — the delta bodies of a delta file get their index too.
         digests=True: the store records a content digest per tensor (digests(), verify(), holds()).  A file written with digests
         (compress_safetensors_file(..., digests=True)) brings them, and they are taken from it — they describe what the WRITER compressed.  A file
         without them is decoded once and the store records what it got: that only pins the state at load — damage that happened before is not seen.
@@ -259,7 +261,7 @@ class ResidentCheckpoint:
         store = cls(dev, entries, blob.numel() + extra, keep=(blob,) + ((base,) if base is not None else ()))
         store._metadata = {k: v for k, v in up.metadata.items() if k not in (safetensors_io.METADATA_KEY, safetensors_io.DIGESTS_KEY, safetensors_io.DELTA_KEY)}
         if index:
-            store.build_index()
+            store.build_index(deltas=(index == "deltas"))
         if recorded is not None:
             missing = [n for n in store.keys() if n not in recorded]
             if missing:
@@ -321,7 +323,8 @@ class ResidentCheckpoint:
     def from_state_dict(cls, sd, device="cuda:0", threshold=0.95, method=None, index=False, base=None, digests=False):
         """Compress the tensors of a state dict on `device` (one batched call) and keep the bodies, trimmed to their lengths and packed at
         256-byte boundaries of one allocation.  A tensor whose body would not be smaller than the tensor itself — and every tensor the codec
-        does not take: integers, float64, empty ones — is kept as it is.  index=True: build_index() on the new store.
+        does not take: integers, float64, empty ones — is kept as it is.  index=True: build_index() on the new store; index="deltas":
+        build_index(deltas=True), which indexes the delta bodies of a variant store as well.
         digests=True: the SOURCE tensors are digested on the device, all of them in one batched launch, before anything is compressed: the store then knows
         what it was built from (digests(), verify(), holds(), the guards of apply_ / revert_).
 
@@ -455,7 +458,7 @@ class ResidentCheckpoint:
         store = cls(dev, [entries[name] for name in sd.keys()], held, keep=keep)
         store._digests = recorded
         if index:
-            store.build_index()
+            store.build_index(deltas=(index == "deltas"))
         return store
 
     # ---- the sync index ---------------------------------------------------------------------------------------------------------
@@ -464,31 +467,38 @@ class ResidentCheckpoint:
     #: No dtype has been timed on a device yet, so none has been taken out.
     INDEX_DTYPES = frozenset(_INDEX_DTYPES)
 
-    def build_index(self, names=None, all_dtypes=False):
+    def build_index(self, names=None, all_dtypes=False, deltas=False):
         """Decode hints for the resident bodies (include/zipnn_hip.h): one pass over each body records where the decoder's sub-blocks
         start — about a byte per 16-24 bytes of Huffman-coded plane — so that every later decode of it (get_tensor, get_tensors, get_slice, plan,
         hook: no further arguments) starts them there instead of finding them by speculation.  The hints sit beside the bodies in device memory,
         never in them, and are advice: the decoded bytes are the same with and without.  names: the tensors to index (default: every compressed
         one); a dtype that measured no gain is left out unless all_dtypes is set.  Tensors already indexed keep their index; plans and hooks made
-        before this call go on decoding without.  The delta bodies of a variant store get none: a launch with a delta base reads no hints."""
+        before this call go on decoding without.
+        deltas=True: the delta bodies of a variant store (info(n)["delta"] is True) get an index as well, of the kind the delta decode reads
+        (ZN_HINT_DELTA: every Huffman-coded plane of a chunk has hints, valid for the delta instances' sub-block sizes) — built against the body where
+        it lies; get_tensor(s), get_slice, plan, hook, verify, apply_ and revert_ then decode those bodies from it, with no further arguments.  A
+        "same" entry holds no body and has nothing to index.  Without it (the default) delta bodies get none."""
         lib = _capi.lib()
         todo = []
         for name in (self.keys() if names is None else names):
             e = self._entries[name]
-            if e.compressed and e.delta is False and e.nbytes and e.hints is None and (all_dtypes or e.dtype in self.INDEX_DTYPES):
+            if e.compressed and e.nbytes and e.hints is None and (all_dtypes or e.dtype in self.INDEX_DTYPES) and (e.delta is False or (deltas and e.delta is True)):
                 todo.append(e)
         if not todo:
             return 0
         with _device_of(self.device):
             stream = _stream_of(self.device)
-            sizes = [lib.hint_size_dev(e.window(0, e.chunks, None), stream) for e in todo]
+
+            def kind(e):                           # (None: the entry points without a kind, as ever)
+                return _capi.HINT_DELTA if e.delta is True else None
+            sizes = [lib.hint_size_dev(e.window(0, e.chunks, None), stream, kind(e)) for e in todo]
             offs, o = [], 0
             for n in sizes:
                 offs.append(o)
                 o += _round_up(n)
             buf = torch.empty(max(o, 1), dtype=torch.uint8, device=self.device)
             for e, n, off in zip(todo, sizes, offs):
-                lib.hint_build_dev(e.window(0, e.chunks, None), buf.data_ptr() + off, n, stream)
+                lib.hint_build_dev(e.window(0, e.chunks, None), buf.data_ptr() + off, n, stream, kind(e))
                 e.hints = buf[off:off + n]
         self._index = (self._index or ()) + (buf,)
         self._index_bytes += o
@@ -518,7 +528,7 @@ class ResidentCheckpoint:
 
         def ptr(dst):                              # (a destination may also be given by its address)
             return dst if isinstance(dst, int) else dst.data_ptr()
-        via, plain, delta = {}, [], []
+        via, plain, delta = {}, [], []                 # (delta: (entry, lo, hi, destination address, base address))
         for e, lo, hi, dst in work:
             if e.delta is False:
                 plain.append((e, lo, hi, dst))
@@ -526,12 +536,12 @@ class ResidentCheckpoint:
             if e.base[0] == "tensor":                  # (a delta entry: "same" over a plain tensor is that tensor, never work)
                 bt = codec.flat_bytes(e.base[1])
                 keep.append(bt)
-                delta.append(e.window(lo, hi, ptr(dst), bt.data_ptr()))
+                delta.append((e, lo, hi, ptr(dst), bt.data_ptr()))
             else:
                 _, bstore, be = e.base
                 via.setdefault(id(bstore), (bstore, []))[1].append((be, lo, hi, dst))
                 if e.delta is True:
-                    delta.append(e.window(lo, hi, ptr(dst), ptr(dst) - lo * e.chunk))
+                    delta.append((e, lo, hi, ptr(dst), ptr(dst) - lo * e.chunk))
         sets = []
         for bstore, w in via.values():
             sets += bstore._launch_sets(w, keep)
@@ -541,10 +551,21 @@ class ResidentCheckpoint:
                 sets.append(("hinted", [e.hinted(lo, hi, ptr(dst)) for e, lo, hi, dst in plain]))
             else:
                 sets.append(("window", [e.window(lo, hi, ptr(dst)) for e, lo, hi, dst in plain]))
-        if delta:
-            sets.append(("window", delta))
+        sets += self._delta_sets(delta, keep)
         keep += [dst for _, _, _, dst in work if not isinstance(dst, int)]
         return sets
+
+    @staticmethod
+    def _delta_sets(delta, keep=None):
+        """delta: [(delta entry, chunk_lo, chunk_hi, destination address, address of the whole tensor's base)] -> their launch set: window items, or — where
+        a body has an index (build_index(deltas=True)) — hinted items of kind HINT_DELTA, which the delta instances read."""
+        if not delta:
+            return []
+        if any(e.hints is not None for e, _, _, _, _ in delta):
+            if keep is not None:
+                keep += [e.hints for e, _, _, _, _ in delta if e.hints is not None]
+            return [("hinted", [e.hinted(lo, hi, d, b) for e, lo, hi, d, b in delta])]
+        return [("window", [e.window(lo, hi, d, b) for e, lo, hi, d, b in delta])]
 
     def _run_sets(self, sets, check):
         """The calls of _launch_sets, in order, on the current stream.  check=False: the sets behind the first add their verdict to the first's
@@ -884,15 +905,13 @@ class ResidentCheckpoint:
             if e.delta == "same" or not e.nbytes:
                 continue
             if e.delta is True:
-                inplace.append(e.window(0, e.chunks, t.data_ptr(), t.data_ptr()))
+                inplace.append((e, 0, e.chunks, t.data_ptr(), t.data_ptr()))
             elif e.compressed:
                 work.append((e, 0, e.chunks, codec.flat_bytes(t)))
             else:
                 t.copy_(e.raw)
             done.append(e.name)
-        sets = self._launch_sets(work)
-        if inplace:
-            sets.append(("window", inplace))
+        sets = self._launch_sets(work) + self._delta_sets(inplace)
         self._run_sets(sets, check)
         return done
 
@@ -908,7 +927,7 @@ class ResidentCheckpoint:
             if e.delta == "same" or not e.nbytes:
                 continue
             if e.delta is True:
-                inplace.append(e.window(0, e.chunks, t.data_ptr(), t.data_ptr()))
+                inplace.append((e, 0, e.chunks, t.data_ptr(), t.data_ptr()))
             elif e.restore is None:
                 stay.append(e.name)
             elif e.restore[0] == "tensor":
@@ -922,8 +941,7 @@ class ResidentCheckpoint:
         sets = []
         for bstore, w in via.values():
             sets += bstore._launch_sets(w)
-        if inplace:
-            sets.append(("window", inplace))
+        sets += self._delta_sets(inplace)
         self._run_sets(sets, check)
         return stay
 
