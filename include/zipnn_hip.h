@@ -293,6 +293,59 @@ typedef struct zn_digest_item { const void* d_src; size_t n; } zn_digest_item;
 int zn_digest_batch_dev(const zn_digest_item* items, size_t count, unsigned long long* d_out, void* stream);
 int zn_digest_host(const void* src, size_t n, unsigned long long* out);
 
+/* CHANGED-ELEMENT PATCHES ("znp1").  huff0 spends at least a bit on every symbol of every plane it codes, so a delta body (tensor ^ base) is never much below
+ * 1/8 of a bf16 tensor however little changed.  A patch is the representation below that floor: the canonical list of the elements that differ from the base,
+ * with their XOR values.  It covers a tensor of n bytes with element size E in {1, 2, 4} (E = the plane count num_buf), n % E == 0, m = n / E < 2^32; anything
+ * else is not eligible (ZN_E_ARG).  Blocks hold 65 536 elements whatever a frame's chunk size; NB = ceil(m / 65536); T = the number of elements whose bytes
+ * differ from the base's.  Everything little-endian, every section at a multiple of 16, padding bytes zero:
+ *
+ *   offset 0                               "ZNP1", u8 E, three zero bytes
+ *   offset 8                               u64 n
+ *   offset 16                              u64 T
+ *   offset 24                              u64 L, the patch's total length
+ *   offset 32                              u32 first[NB + 1]: entries in front of block b; first[NB] == T
+ *   A1 = round16(32 + 4 (NB + 1))          u16 off[T]: the element's offset inside its block, strictly ascending within a block
+ *   A2 = round16(A1 + 2 T)                 val[T], E bytes each: tensor ^ base at that element, never zero
+ *   L  = A2 + E T
+ *
+ * The patch of a (tensor, base) pair is UNIQUE: exactly the differing elements, in ascending order — every schedule produces the same bytes.  Applying is
+ * dst[e] ^= val; the same patch applied twice gives the base back.
+ * zn_patch_len: L for (n, elem, T) — 0 when (n, elem) is not eligible or T > m.
+ * zn_patch_size_batch_dev: the count pass alone — sizes_out[i] = L of item i, or 0 when its bytes are the base's (T == 0); one read-back of all lengths.
+ * zn_patch_build_batch_dev: count, scan and emit; patch_len = L, or 0 (nothing written) for an identical item; d_patch 16-byte aligned; ZN_E_CAP when a capacity
+ *   is short (patch_len then holds what every item needs and nothing was written).  Both are synchronous, like compress; d_src / d_base at any elem-aligned
+ *   address (16-byte loads when both are 16-byte aligned).  The source must not change during the call; if it does the patch is wrong, never the memory around it.
+ * zn_patch_apply_batch_dev: one launch for the batch.  Only the entries inside the byte window [byte_lo, byte_hi) (multiples of elem, byte_hi <= n) are applied;
+ *   d_dst (elem-aligned) is where the window's first byte lies and receives that range.  d_base == NULL: in place, d_dst ^= patch.  Otherwise the window's bytes
+ *   are first copied from d_base + byte_lo on the stream.  An empty window and a patch with T == 0 are valid.  d_patch 16-byte aligned, patch_len >= 32 (else
+ *   ZN_E_ARG).  A patch may come from anywhere: the kernel writes nothing outside the window, reads nothing outside [d_patch, d_patch + patch_len), and reports
+ *   ZN_E_CORRUPT through the call's status slot — check, zn_decode_status, zn_decode_status_chain, exactly as decodes do — for a header that disagrees with the
+ *   item (E, n, L against patch_len), a first[] that decreases or exceeds T, an offset beyond the tensor's last element, offsets not strictly ascending inside a
+ *   block, or a zero value.  (first[] is checked for the blocks the window touches.)  A wrong patch costs the verdict, never a byte outside the destination;
+ *   the destination itself is then undefined.
+ * zn_patch_plan_*: mirror zn_plan_*: the table lives in device memory the plan owns, a run launches only (and enqueues the base copies of items with d_base), its
+ *   verdict joins a chain when the thread has one open; the plan refers to patches, destinations and bases by address. */
+typedef struct zn_patch_size_item { const void* d_src; const void* d_base; size_t n; int elem; } zn_patch_size_item;
+typedef struct zn_patch_build_item {
+  const void* d_src; const void* d_base; size_t n; int elem;
+  void* d_patch; size_t patch_cap;
+  size_t patch_len;                         /* out */
+} zn_patch_build_item;
+typedef struct zn_patch_apply_item {
+  const void* d_patch; size_t patch_len;
+  size_t n; int elem;                       /* of the whole tensor */
+  size_t byte_lo, byte_hi;
+  void* d_dst; const void* d_base;
+} zn_patch_apply_item;
+typedef struct zn_patch_plan zn_patch_plan;
+size_t zn_patch_len(size_t n, int elem, size_t entries);
+int zn_patch_size_batch_dev(const zn_patch_size_item* items, size_t count, size_t* sizes_out, void* stream);
+int zn_patch_build_batch_dev(zn_patch_build_item* items, size_t count, void* stream);
+int zn_patch_apply_batch_dev(const zn_patch_apply_item* items, size_t count, void* stream, int check);
+int zn_patch_plan_create(const zn_patch_apply_item* items, size_t count, zn_patch_plan** plan);
+int zn_patch_plan_run(zn_patch_plan* plan, void* stream, int check);
+int zn_patch_plan_destroy(zn_patch_plan* plan);
+
 /* Plumbing for callers that keep the tensors in HBM but hold pageable host buffers (files, Python bytes): the same
  * pinned, multi-threaded transfer the host-buffer entry points above use internally (zipnn_amd/csrc/zn_host_pipe.hpp),
  * on the current device; returns when the n bytes have arrived.  No reference counterpart — the reference's buffers

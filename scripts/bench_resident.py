@@ -34,6 +34,9 @@ blocks of leg b as the base, the two fine-tunes of --delta:
 --delta-index: the sync index of variant stores instead (build_index(deltas=True), DESIGN §3.6 "Two kinds"), into profiles/resident_delta_index.{json,txt}:
   p  per fine-tune of --delta: plan.run of one block from a variant over a resident indexed base, without and with the variant's DELTA index, interleaved in
      both orders (A B A B B A B A: the four runs without are the A/A spread), the build time of the DELTA index and its size
+--sparse: sparse variant stores instead (from_state_dict(..., base=..., sparse=True)), into profiles/resident_sparse.{json,txt}:
+  s  per fine-tune of --delta, over a resident indexed base: resident bytes and build time without and with sparse=True; plan.run of one block from either
+     store, interleaved in both orders (A B A B B A B A: the four runs of the delta store are the A/A spread); apply_ + revert_ of one block from either
 """
 import argparse
 import json
@@ -675,6 +678,87 @@ def main_delta_index(args):
     return 0
 
 
+def leg_s(args):
+    """--sparse: the two fine-tunes of --delta as variant stores over a resident indexed base, built without and with sparse=True: resident bytes,
+    build time, plan.run of one block from either store — interleaved, both orders (A B A B, then B A B A) —, apply_ + revert_ on live tensors from either."""
+    import torch
+    from zipnn_amd import ResidentCheckpoint
+    sd, per = _blocks(args.layers)
+    names = per[0]
+    res = {"layers": args.layers, "block_bytes": sum(sd[k].numel() * 2 for k in names), "fine_tunes": []}
+    base = ResidentCheckpoint.from_state_dict(sd, "cuda:0", index=True)
+
+    def timed(fn):
+        torch.cuda.synchronize(); t0 = time.perf_counter(); r = fn(); torch.cuda.synchronize()
+        return r, time.perf_counter() - t0
+    for kind in ("sparse", "drift"):
+        ft = _fine_tune(sd, kind, 21)
+        stores, build_s = {}, {}
+        stores["delta"], build_s["delta"] = timed(lambda: ResidentCheckpoint.from_state_dict(ft, "cuda:0", base=base))
+        stores["sparse"], build_s["sparse"] = timed(lambda: ResidentCheckpoint.from_state_dict(ft, "cuda:0", base=base, sparse=True))
+        sp = stores["sparse"]
+        scratch = torch.empty(sp.scratch_bytes(names), dtype=torch.uint8, device="cuda")
+        runs, kernels = {"delta": [], "sparse": []}, {}
+        for leg in ("delta", "sparse", "delta", "sparse", "sparse", "delta", "sparse", "delta"):
+            plan = stores[leg].plan(names, into=scratch)
+            t = _events_ms(plan.run, args.reps)
+            plan.status()
+            for k in names:
+                assert _same(plan.tensors[k], ft[k]), (kind, leg, k)
+            runs[leg].append(t["median_ms"])
+            kernels[leg] = _capi_kernels()
+            plan.close()
+        ar, ar_kernels = {}, {}
+        for leg in ("delta", "sparse"):
+            live = {k: sd[k].clone() for k in names}
+            st = stores[leg]
+            ar[leg] = _events_ms(lambda: (st.apply_(live, check=False), st.revert_(live, check=False)), args.reps)["median_ms"]
+            st.status()
+            for k in names:
+                assert _same(live[k], sd[k]), (kind, leg, "revert", k)
+            st.apply_(live)
+            ar_kernels[leg] = _capi_kernels()
+            for k in names:
+                assert _same(live[k], ft[k]), (kind, leg, "apply", k)
+            del live
+        a, s = runs["delta"], runs["sparse"]
+        res["fine_tunes"].append({"kind": kind, "tensors": len(ft), "nbytes": sp.nbytes, "sparse_entries": sum(1 for k in ft if sp.info(k)["delta"] == "sparse"),
+                                  "patch_entries": sum(sp.info(k)["patch_entries"] or 0 for k in ft),
+                                  "resident_bytes": {leg: stores[leg].resident_bytes for leg in stores}, "build_s": build_s, "plan_run_ms": runs, "kernels": kernels,
+                                  "aa_spread": (max(a) - min(a)) / min(a), "gain": 1.0 - (sum(s) / len(s)) / (sum(a) / len(a)),
+                                  "apply_revert_ms": ar, "apply_kernels": ar_kernels})
+        del stores, sp, ft, scratch
+        torch.cuda.empty_cache()
+    return res
+
+
+def main_sparse(args):
+    p = subprocess.run(["timeout", "-k", "10", "540", sys.executable, os.path.abspath(__file__), "--leg", "s", "--layers", str(args.layers), "--reps", str(args.reps)],
+                       capture_output=True, text=True)
+    line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+    if p.returncode != 0 or not line:
+        print(f"leg s failed (exit {p.returncode})\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}")
+        return 1
+    res = json.loads(line[0][7:])
+    out = args.out if args.out != os.path.join(ROOT, "profiles", "resident_decode") else os.path.join(ROOT, "profiles", "resident_sparse")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    lines = [f"command: python scripts/bench_resident.py --sparse --layers {args.layers} --reps {args.reps}",
+             "sparse variant probe (ResidentCheckpoint.from_state_dict(..., base=..., sparse=True)): the fine-tunes of --delta over a resident indexed base, built without (delta)",
+             "and with sparse=True; plan.run of one Llama-3-8B block (bf16), interleaved in both orders (A B A B B A B A), device events, median ms; every result checked"]
+    for r in res["fine_tunes"]:
+        q, b = r["plan_run_ms"], r["resident_bytes"]
+        lines.append(f"  {r['kind']:<7} {r['sparse_entries']} of {r['tensors']} tensors sparse ({r['patch_entries']} entries): resident {b['sparse']} B against {b['delta']} B"
+                     f" = {b['sparse'] / b['delta']:.3f} of the delta store, {b['sparse'] / r['nbytes']:.4f} of the raw bytes; built in {r['build_s']['sparse']:.3f} s against {r['build_s']['delta']:.3f} s")
+        lines.append("          plan.run delta " + " / ".join(f"{x:.4f}" for x in q["delta"]) + "   sparse " + " / ".join(f"{x:.4f}" for x in q["sparse"]) +
+                     f"   gain {100 * r['gain']:+.1f} %  (A/A spread of the delta runs: {100 * r['aa_spread']:.1f} %)")
+        lines.append(f"          apply_ + revert_ of the block on live tensors: delta {r['apply_revert_ms']['delta']:.4f} ms, sparse {r['apply_revert_ms']['sparse']:.4f} ms")
+        lines.append(f"          kernels delta [{r['kernels']['delta']}]  sparse [{r['kernels']['sparse']}]  apply_ sparse [{r['apply_kernels']['sparse']}]")
+    open(out + ".txt", "w").write("\n".join(lines) + "\n")
+    json.dump(res, open(out + ".json", "w"), indent=1)
+    print("\n".join(lines))
+    return 0
+
+
 def main_index(args):
     results = {}
     for leg, limit in INDEX_LEG_SECONDS.items():
@@ -716,6 +800,7 @@ def main():
     ap.add_argument("--digest", action="store_true", help="the content digest leg (m) instead of a-e")
     ap.add_argument("--delta-file", action="store_true", help="the delta file leg (n) instead of a-e")
     ap.add_argument("--delta-index", action="store_true", help="the DELTA sync index leg (p) instead of a-e")
+    ap.add_argument("--sparse", action="store_true", help="the sparse variant leg (s) instead of a-e")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resident_decode"))
     args = ap.parse_args()
     if args.leg:                                          # a child: one leg, its result as one JSON line
@@ -731,6 +816,8 @@ def main():
         return main_delta_file(args)
     if args.delta_index:
         return main_delta_index(args)
+    if args.sparse:
+        return main_sparse(args)
     results = {}
     for leg, limit in LEG_SECONDS.items():
         p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--layers", str(args.layers), "--reps", str(args.reps)],

@@ -81,6 +81,26 @@ class ZnDigestItem(ctypes.Structure):
     _fields_ = [("d_src", ctypes.c_void_p), ("n", ctypes.c_size_t)]
 
 
+class ZnPatchSizeItem(ctypes.Structure):
+    """struct zn_patch_size_item of include/zipnn_hip.h"""
+    _fields_ = [("d_src", ctypes.c_void_p), ("d_base", ctypes.c_void_p), ("n", ctypes.c_size_t), ("elem", ctypes.c_int)]
+
+
+class ZnPatchBuildItem(ctypes.Structure):
+    """struct zn_patch_build_item of include/zipnn_hip.h"""
+    _fields_ = [("d_src", ctypes.c_void_p), ("d_base", ctypes.c_void_p), ("n", ctypes.c_size_t), ("elem", ctypes.c_int),
+                ("d_patch", ctypes.c_void_p), ("patch_cap", ctypes.c_size_t), ("patch_len", ctypes.c_size_t)]
+
+
+class ZnPatchApplyItem(ctypes.Structure):
+    """struct zn_patch_apply_item of include/zipnn_hip.h"""
+    _fields_ = [("d_patch", ctypes.c_void_p), ("patch_len", ctypes.c_size_t), ("n", ctypes.c_size_t), ("elem", ctypes.c_int),
+                ("byte_lo", ctypes.c_size_t), ("byte_hi", ctypes.c_size_t), ("d_dst", ctypes.c_void_p), ("d_base", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(ZnPatchApplyItem) == 64
+
+
 class ZnLib:
     """A loaded libzipnn_hip.so."""
 
@@ -177,6 +197,21 @@ class ZnLib:
         L.zn_digest_batch_dev.argtypes = [ctypes.POINTER(ZnDigestItem), sz, vp, vp]
         L.zn_digest_host.restype = ci
         L.zn_digest_host.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_ulonglong)]
+        if hasattr(L, "zn_patch_len"):          # (a library built from an earlier commit, loaded beside this one by the A/B scripts, has no patches)
+            L.zn_patch_len.restype = sz
+            L.zn_patch_len.argtypes = [sz, ci, sz]
+            L.zn_patch_size_batch_dev.restype = ci
+            L.zn_patch_size_batch_dev.argtypes = [ctypes.POINTER(ZnPatchSizeItem), sz, ctypes.POINTER(sz), vp]
+            L.zn_patch_build_batch_dev.restype = ci
+            L.zn_patch_build_batch_dev.argtypes = [ctypes.POINTER(ZnPatchBuildItem), sz, vp]
+            L.zn_patch_apply_batch_dev.restype = ci
+            L.zn_patch_apply_batch_dev.argtypes = [ctypes.POINTER(ZnPatchApplyItem), sz, vp, ci]
+            L.zn_patch_plan_create.restype = ci
+            L.zn_patch_plan_create.argtypes = [ctypes.POINTER(ZnPatchApplyItem), sz, vpp]
+            L.zn_patch_plan_run.restype = ci
+            L.zn_patch_plan_run.argtypes = [vp, vp, ci]
+            L.zn_patch_plan_destroy.restype = ci
+            L.zn_patch_plan_destroy.argtypes = [vp]
         L.zn_copy_to_device.restype = ci; L.zn_copy_to_device.argtypes = [vp, vp, sz]
         L.zn_copy_to_host.restype = ci; L.zn_copy_to_host.argtypes = [vp, vp, sz]
         L.zn_release_workspace.restype = ci
@@ -550,6 +585,61 @@ class ZnLib:
         out = ctypes.c_ulonglong(0)
         self._check(self._L.zn_digest_host(cb.addr, mv.nbytes, ctypes.byref(out)))
         return int(out.value)
+
+    # -- changed-element patches ("znp1", include/zipnn_hip.h) --
+    def patch_len(self, n, elem, entries):
+        """zn_patch_len: the length of a patch of `entries` elements for a tensor of n bytes, elem bytes per element (0: not eligible)."""
+        return int(self._L.zn_patch_len(n, elem, entries))
+
+    def patch_size_batch_dev(self, items, stream=0):
+        """zn_patch_size_batch_dev.  items: iterable of (src_ptr, base_ptr, n, elem) -> the patches' lengths (0: the bytes are the base's); the count pass only."""
+        items = list(items)
+        arr = (ZnPatchSizeItem * max(len(items), 1))()
+        for i, (sp, bp, n, el) in enumerate(items):
+            arr[i].d_src = sp or None; arr[i].d_base = bp or None; arr[i].n = n; arr[i].elem = el
+        out = (ctypes.c_size_t * max(len(items), 1))()
+        self._check(self._L.zn_patch_size_batch_dev(arr, len(items), out, ctypes.c_void_p(stream or None)))
+        return [int(out[i]) for i in range(len(items))]
+
+    def patch_build_batch_dev(self, items, stream=0):
+        """zn_patch_build_batch_dev.  items: iterable of (src_ptr, base_ptr, n, elem, patch_ptr, patch_cap) -> the patches' lengths (0: identical, nothing written)."""
+        items = list(items)
+        arr = (ZnPatchBuildItem * max(len(items), 1))()
+        for i, (sp, bp, n, el, pp, cap) in enumerate(items):
+            arr[i].d_src = sp or None; arr[i].d_base = bp or None; arr[i].n = n; arr[i].elem = el
+            arr[i].d_patch = pp or None; arr[i].patch_cap = cap
+        self._check(self._L.zn_patch_build_batch_dev(arr, len(items), ctypes.c_void_p(stream or None)))
+        return [int(arr[i].patch_len) for i in range(len(items))]
+
+    @staticmethod
+    def _patch_apply_items(items):
+        items = list(items)
+        arr = (ZnPatchApplyItem * max(len(items), 1))()
+        for i, it in enumerate(items):
+            pp, pl, n, el, lo, hi, dp = it[:7]
+            arr[i].d_patch = pp or None; arr[i].patch_len = pl; arr[i].n = n; arr[i].elem = el
+            arr[i].byte_lo = lo; arr[i].byte_hi = hi; arr[i].d_dst = dp or None
+            arr[i].d_base = (it[7] or None) if len(it) > 7 else None
+        return arr, len(items)
+
+    def patch_apply_batch_dev(self, items, stream=0, check=True):
+        """zn_patch_apply_batch_dev.  items: iterable of (patch_ptr, patch_len, n, elem, byte_lo, byte_hi, dst_ptr[, base_ptr]): the entries inside the byte
+        window are XORed into dst_ptr (where the window's first byte lies) — in place, or over a copy of the base's window when base_ptr is given."""
+        arr, n = self._patch_apply_items(items)
+        self._check(self._L.zn_patch_apply_batch_dev(arr, n, ctypes.c_void_p(stream or None), 1 if check else 0))
+
+    def patch_plan_create(self, items):
+        """zn_patch_plan_create over items as for patch_apply_batch_dev -> an opaque handle (patch_plan_run / patch_plan_destroy)."""
+        arr, n = self._patch_apply_items(items)
+        h = ctypes.c_void_p(None)
+        self._check(self._L.zn_patch_plan_create(arr, n, ctypes.byref(h)))
+        return h
+
+    def patch_plan_run(self, plan, stream=0, check=True):
+        self._check(self._L.zn_patch_plan_run(plan, ctypes.c_void_p(stream or None), 1 if check else 0))
+
+    def patch_plan_destroy(self, plan):
+        self._check(self._L.zn_patch_plan_destroy(plan))
 
     def decode_status(self, stream=0):
         """zn_decode_status: wait for `stream`, raise what the last check=False decode call on this device would have raised."""

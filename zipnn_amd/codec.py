@@ -249,6 +249,76 @@ def build_decode_hints(lib, items):
     return out
 
 
+# ---- changed-element patches ("znp1": include/zipnn_hip.h) -------------------------------------------------------------------
+def patch_elem(t):
+    """-> the element size a patch of tensor `t` is built with (1, 2 or 4), or None where a patch cannot describe it (other element sizes, 2^32 elements or more)."""
+    es = t.element_size()
+    return es if es in (1, 2, 4) and t.numel() < (1 << 32) else None
+
+
+def patch_sizes_device_batch(lib, pairs):
+    """pairs: [(flat uint8 source, flat uint8 base, elem)] on one device -> the lengths of their patches (0: identical bytes): the count pass alone, one read-back."""
+    pairs = list(pairs)
+    if not pairs:
+        return []
+    dev = pairs[0][0].device
+    with torch.cuda.device(dev) if dev.type == "cuda" else _nullctx():
+        return lib.patch_size_batch_dev([(s.data_ptr() if s.numel() else 0, b.data_ptr() if s.numel() else 0, s.numel(), el) for s, b, el in pairs], _stream_handle(pairs[0][0]))
+
+
+def patch_build_device_batch(lib, pairs, sizes=None):
+    """pairs: [(flat uint8 source, flat uint8 base, elem)] on one device -> their patches: uint8 tensors (views of one allocation, each at a multiple of 256
+    bytes), None where the bytes are identical.  sizes: the lengths patch_sizes_device_batch gave for the same pairs (else they are counted here)."""
+    pairs = list(pairs)
+    if not pairs:
+        return []
+    for s, b, _ in pairs:
+        if s.dtype != torch.uint8 or b.dtype != torch.uint8 or s.numel() != b.numel() or s.device != b.device or not s.is_contiguous() or not b.is_contiguous():
+            raise ValueError("patch: contiguous uint8 views of the same length on one device")
+    if sizes is None:
+        sizes = patch_sizes_device_batch(lib, pairs)
+    dev = pairs[0][0].device
+    offs, o = [], 0
+    for n in sizes:
+        offs.append(o)
+        o += (n + 255) // 256 * 256
+    arena = torch.empty(max(o, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev) if dev.type == "cuda" else _nullctx():
+        lens = lib.patch_build_batch_dev([(s.data_ptr() if s.numel() else 0, b.data_ptr() if s.numel() else 0, s.numel(), el, arena.data_ptr() + off, n)
+                                          for (s, b, el), off, n in zip(pairs, offs, sizes)], _stream_handle(arena))
+    return [arena[off:off + n] if n else None for off, n in zip(offs, lens)]
+
+
+def patch_build(t, base):
+    """The "znp1" patch (include/zipnn_hip.h) that turns `base` into `t`: the elements whose bytes differ, with their XOR values — a uint8 tensor on the
+    tensors' device, or None when the bytes are identical.  t and base: the same dtype (1, 2 or 4 bytes per element) and shape, on one device."""
+    from . import _capi
+    if t.dtype != base.dtype or tuple(t.shape) != tuple(base.shape) or t.device != base.device:
+        raise ValueError("patch_build: two tensors of the same dtype and shape on one device")
+    el = patch_elem(t)
+    if el is None:
+        raise ValueError(f"patch_build: {t.dtype} with {t.numel()} elements is not eligible (elements of 1, 2 or 4 bytes, fewer than 2^32 of them)")
+    return patch_build_device_batch(_capi.lib(), [(flat_bytes(t.detach()), flat_bytes(base.detach()), el)])[0]
+
+
+def patch_apply_(t, patch, check=True):
+    """t ^= patch, in place: a tensor that holds the base's values holds the fine-tune's afterwards, and the base's again after a second call.  patch: what
+    patch_build returned (None: nothing to do).  A malformed patch raises (ZN_E_CORRUPT / ZN_E_ARG) and never writes outside `t`.  -> t"""
+    from . import _capi
+    if patch is None:
+        return t
+    d = t.detach()
+    el = patch_elem(d)
+    if el is None or not d.is_contiguous():
+        raise ValueError("patch_apply_: a contiguous tensor with elements of 1, 2 or 4 bytes")
+    if patch.dtype != torch.uint8 or patch.device != d.device or not patch.is_contiguous():
+        raise ValueError("patch_apply_: the patch is a contiguous uint8 tensor on the tensor's device")
+    n = d.numel() * el
+    with torch.cuda.device(d.device) if d.is_cuda else _nullctx():
+        _capi.lib().patch_apply_batch_dev([(patch.data_ptr(), patch.numel(), n, el, 0, n, d.data_ptr() if n else 0)], _stream_handle(d), check)
+    return t
+
+
 # ---- content digests ("zn64-1": include/zipnn_hip.h, DESIGN §3.8) -------------------------------------------------------------------------
 DIGEST_ALGO = "zn64-1"
 

@@ -996,3 +996,6 @@ int zn_release_workspace(void) {
 }
 
 }  // extern "C"
+
+// (for zn_patch.hip's apply calls, which report through the decode calls' status slots)
+uint32_t* zn_take_status_slot(Workspace& w, int dev, int check, bool* chain) { return decode_status_slot(w, dev, check, chain); }

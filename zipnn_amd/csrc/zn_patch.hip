@@ -1,0 +1,495 @@
+// zn_patch.hip — changed-element patches ("znp1", include/zipnn_hip.h): the elements of a tensor that differ from a base, with their XOR values.
+//
+//   zn_k_patch_count   one workgroup per block of 65 536 elements: how many of them differ (one word per block)
+//   zn_k_patch_scan    one workgroup per item: the block counts become first[] (an exclusive prefix sum, in place), the item's T goes to its total
+//   zn_k_patch_emit    one workgroup per block again: off / val of the block's differing elements at first[b] + rank, in ascending order; block 0 writes the header
+//   zn_k_patch_apply   one workgroup per block of the window: dst[e] ^= val for the block's entries inside the window, after checking everything it reads
+//
+// Count and emit are ONE body (zn_pa_block<E, EMIT>): the same loads, the same comparison, the same order of elements.  The emit instance never writes outside
+// [first[b], first[b + 1]) of off / val: if the source changed between the two passes the patch is wrong, not the memory around it.  A thread takes 16 consecutive
+// bytes per step (one 16-byte load each of source and base when both are 16-byte aligned and the bytes lie inside the tensor; element loads otherwise), so that
+// ranks ascend with the thread index: a wave-exclusive scan of the per-thread counts, the waves' sums through LDS, a running total in a register.
+// The apply kernel trusts nothing: a patch may come from anywhere.  It reads only inside [patch, patch + patch_len) — the header first, whose L must be patch_len
+// and the formula's value for its T, which bounds every later index — and writes only elements of the window; what is wrong costs the verdict (ZN_DEV_CORRUPT).
+#include "zn_workspace.hpp"
+
+#include <memory>
+#include <vector>
+
+#define ZN_PA_THREADS 256u
+#define ZN_PA_WAVES (ZN_PA_THREADS / 64u)
+
+template <uint32_t E> struct ZnPaElem;
+template <> struct ZnPaElem<1> { typedef uint8_t t; };
+template <> struct ZnPaElem<2> { typedef uint16_t t; };
+template <> struct ZnPaElem<4> { typedef uint32_t t; };
+
+template <typename S>
+__device__ __forceinline__ S zn_pa_find(const S& one, const S* __restrict__ segs, uint32_t nseg, uint32_t b) {
+  if (segs == nullptr) return one;
+  uint32_t lo = 0, hi = nseg;
+  while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (segs[mid].wg0 <= b) lo = mid; else hi = mid; }
+  return segs[lo];
+}
+
+// inclusive sum over the lanes of a wave (lane 63 holds the wave's total); skipped where no lane of the wave brings anything
+__device__ __forceinline__ uint32_t zn_pa_wave_incl(uint32_t v, uint32_t lane) {
+  if (__ballot(v != 0u) == 0ull) return 0u;
+#pragma unroll
+  for (uint32_t d = 1; d < 64u; d <<= 1) { const uint32_t t = __shfl_up(v, d); if (lane >= d) v += t; }
+  return v;
+}
+
+// src ^ base of the 16 / E elements from element e0 on, as the four little-endian words they occupy (elements at or behind m: zero) -> the mask of those that differ
+template <uint32_t E>
+__device__ __forceinline__ uint32_t zn_pa_diff(const uint8_t* __restrict__ src, const uint8_t* __restrict__ base, uint64_t e0, uint64_t m, bool fast, uint32_t (&x)[4]) {
+  typedef typename ZnPaElem<E>::t T;
+  constexpr uint32_t V = 16u / E;
+  if (fast && e0 + V <= m) {
+    const uint4 a = *(const uint4*)(src + e0 * E), b = *(const uint4*)(base + e0 * E);
+    x[0] = a.x ^ b.x; x[1] = a.y ^ b.y; x[2] = a.z ^ b.z; x[3] = a.w ^ b.w;
+  } else {
+    x[0] = x[1] = x[2] = x[3] = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < V; k++)
+      if (e0 + k < m) {
+        const T d = (T)(((const T*)src)[e0 + k] ^ ((const T*)base)[e0 + k]);
+        x[(k * E) >> 2] |= (uint32_t)d << (8u * ((k * E) & 3u));
+      }
+  }
+  uint32_t mask = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < V; k++) {
+    const uint32_t d = (x[(k * E) >> 2] >> (8u * ((k * E) & 3u))) & (E == 4u ? 0xFFFFFFFFu : (1u << (8u * (E & 3u))) - 1u);
+    if (d) mask |= 1u << k;
+  }
+  return mask;
+}
+
+// Block b of one item.  !EMIT: words[b] = its number of differing elements.  EMIT: words[] is first[]; the block's entries go to off / val of the patch.
+template <uint32_t E, bool EMIT>
+__device__ __forceinline__ void zn_pa_block(const ZnPatchBSeg& sg, uint32_t b, uint32_t* __restrict__ words, uint32_t (*part)[ZN_PA_WAVES]) {
+  typedef typename ZnPaElem<E>::t T;
+  constexpr uint32_t V = 16u / E, STEP = ZN_PA_THREADS * V;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint8_t* src = ZN_GLOBAL_PTR(const uint8_t, sg.src);
+  const uint8_t* base = ZN_GLOBAL_PTR(const uint8_t, sg.base);
+  const uint64_t m = sg.m, blk0 = (uint64_t)b * ZN_PATCH_BLOCK;
+  const uint32_t left = m - blk0 >= (uint64_t)ZN_PATCH_BLOCK ? ZN_PATCH_BLOCK : (uint32_t)(m - blk0);      // > 0: the grid has no workgroup for a block without elements
+  const uint32_t steps = (left + STEP - 1u) / STEP;
+  const bool fast = ((((uintptr_t)src) | ((uintptr_t)base)) & 15u) == 0u;        // (per item: wave-uniform)
+  uint32_t lo = 0, hi = 0;
+  uint16_t* off = nullptr; T* val = nullptr;
+  if (EMIT) {
+    const uint64_t nb = zn_patch_blocks(m), total = words[nb];
+    uint8_t* p = ZN_GLOBAL_PTR(uint8_t, sg.patch);
+    const uint64_t a1 = zn_patch_a1(nb), a2 = zn_patch_a2(nb, total);
+    lo = words[b]; hi = words[b + 1u];
+    if (tid == 0) {
+      uint32_t* first = (uint32_t*)(p + 32);
+      first[b] = lo;
+      if (b + 1u == nb) first[nb] = (uint32_t)total;
+      if (b == 0) {                              // the header, and the zero padding in front of off[] and of val[]
+        *(uint32_t*)p = ZN_PATCH_MAGIC; *(uint32_t*)(p + 4) = E;
+        *(uint64_t*)(p + 8) = m * E; *(uint64_t*)(p + 16) = total; *(uint64_t*)(p + 24) = a2 + (uint64_t)E * total;
+        for (uint64_t i = 32u + 4u * (nb + 1u); i < a1; i++) p[i] = 0;
+        for (uint64_t i = a1 + 2u * total; i < a2; i++) p[i] = 0;
+      }
+    }
+    if (hi <= lo) return;                        // (workgroup-uniform) nothing of this block differs
+    off = (uint16_t*)(p + a1); val = (T*)(p + a2);
+  }
+  uint32_t run = 0;                              // count: this thread's differing elements; emit: the block's entries in front of this step
+  for (uint32_t s = 0; s < steps; s++) {
+    const uint32_t o0 = s * STEP + tid * V;      // offset of the thread's first element inside the block
+    uint32_t x[4];
+    const uint32_t mask = zn_pa_diff<E>(src, base, blk0 + o0, m, fast, x);
+    const uint32_t cnt = (uint32_t)__popc(mask);
+    if (!EMIT) { run += cnt; continue; }
+    const uint32_t incl = zn_pa_wave_incl(cnt, lane);
+    if (lane == 63u) part[s & 1u][wave] = incl;  // (two sets of slots: one barrier per step is enough)
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < ZN_PA_WAVES; w++) { const uint32_t q = part[s & 1u][w]; if (w < wave) before += q; all += q; }
+    if (cnt) {
+      uint32_t pos = lo + run + before + incl - cnt;
+#pragma unroll
+      for (uint32_t k = 0; k < V; k++)
+        if ((mask >> k) & 1u) {
+          if (pos < hi) {                        // never outside the block's own range, whatever the source holds by now
+            off[pos] = (uint16_t)(o0 + k);
+            val[pos] = (T)(x[(k * E) >> 2] >> (8u * ((k * E) & 3u)));
+          }
+          pos++;
+        }
+    }
+    run += all;
+  }
+  if (!EMIT) {
+    uint32_t v = run;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    if (lane == 0) part[0][wave] = v;
+    __syncthreads();
+    if (tid == 0) { uint32_t c = 0; for (uint32_t w = 0; w < ZN_PA_WAVES; w++) c += part[0][w]; words[b] = c; }
+  }
+}
+
+template <bool EMIT>
+__device__ __forceinline__ void zn_pa_dispatch(const ZnPatchBSeg& one, const ZnPatchBSeg* __restrict__ segs_, uint32_t nseg, uint32_t* words_, uint32_t (*part)[ZN_PA_WAVES]) {
+  const ZnPatchBSeg* segs = ZN_GLOBAL_PTR(const ZnPatchBSeg, segs_);
+  const ZnPatchBSeg sg = zn_pa_find(one, segs, nseg, blockIdx.x);
+  uint32_t* words = ZN_GLOBAL_PTR(uint32_t, words_) + sg.w0;
+  const uint32_t b = blockIdx.x - sg.wg0;
+  if (sg.E == 1u) zn_pa_block<1, EMIT>(sg, b, words, part);
+  else if (sg.E == 2u) zn_pa_block<2, EMIT>(sg, b, words, part);
+  else zn_pa_block<4, EMIT>(sg, b, words, part);
+}
+
+__global__ void __launch_bounds__(ZN_PA_THREADS) zn_k_patch_count(const ZnPatchBSeg one, const ZnPatchBSeg* __restrict__ segs, uint32_t nseg, uint32_t* __restrict__ words) {
+  __shared__ uint32_t part[2][ZN_PA_WAVES];
+  zn_pa_dispatch<false>(one, segs, nseg, words, part);
+}
+
+__global__ void __launch_bounds__(ZN_PA_THREADS) zn_k_patch_emit(const ZnPatchBSeg one, const ZnPatchBSeg* __restrict__ segs, uint32_t nseg, uint32_t* __restrict__ words) {
+  __shared__ uint32_t part[2][ZN_PA_WAVES];
+  zn_pa_dispatch<true>(one, segs, nseg, words, part);
+}
+
+// one workgroup per item: its block counts -> first[] (in place), first[NB] = T, totals[item] = T
+__global__ void __launch_bounds__(ZN_PA_THREADS) zn_k_patch_scan(const ZnPatchBSeg one, const ZnPatchBSeg* __restrict__ segs_, uint32_t* __restrict__ words_, uint64_t* __restrict__ totals) {
+  __shared__ uint32_t part[ZN_PA_WAVES];
+  const ZnPatchBSeg* segs = ZN_GLOBAL_PTR(const ZnPatchBSeg, segs_);
+  const ZnPatchBSeg sg = segs ? segs[blockIdx.x] : one;
+  uint32_t* words = ZN_GLOBAL_PTR(uint32_t, words_) + sg.w0;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t nb = (uint32_t)zn_patch_blocks(sg.m);
+  uint32_t run = 0;
+  for (uint32_t i0 = 0; i0 < nb; i0 += ZN_PA_THREADS) {
+    const uint32_t i = i0 + tid;
+    const uint32_t c = i < nb ? words[i] : 0u;
+    const uint32_t incl = zn_pa_wave_incl(c, lane);
+    if (lane == 63u) part[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < ZN_PA_WAVES; w++) { const uint32_t q = part[w]; if (w < wave) before += q; all += q; }
+    if (i < nb) words[i] = run + before + incl - c;
+    run += all;
+    __syncthreads();
+  }
+  if (tid == 0) { words[nb] = run; totals[blockIdx.x] = run; }
+}
+
+template <uint32_t E>
+__device__ __forceinline__ void zn_pa_apply_block(const ZnPatchASeg& sg, uint32_t b, uint32_t* __restrict__ status) {
+  typedef typename ZnPaElem<E>::t T;
+  const uint32_t tid = threadIdx.x;
+  const uint8_t* p = ZN_GLOBAL_PTR(const uint8_t, sg.patch);
+  const uint64_t n = sg.n, m = n / E, nb = zn_patch_blocks(m);                   // (the host has checked: n % E == 0, m < 2^32, patch_len >= 32, b < nb)
+  // the header must describe this item, and its L — the formula's value for its T — must be the length we were given: every index below T then lies inside
+  const uint32_t magic = *(const uint32_t*)p, e = *(const uint32_t*)(p + 4);
+  const uint64_t hn = *(const uint64_t*)(p + 8), total = *(const uint64_t*)(p + 16), len = *(const uint64_t*)(p + 24);
+  bool bad = magic != ZN_PATCH_MAGIC || e != E || hn != n || total > m || len != sg.patch_len;
+  if (!bad) bad = zn_patch_total(m, E, total) != len;
+  uint32_t f0 = 0, f1 = 0;
+  if (!bad) {
+    const uint32_t* first = (const uint32_t*)(p + 32);
+    f0 = first[b]; f1 = first[b + 1u];
+    bad = f0 > f1 || (uint64_t)f1 > total || (b == 0 && f0 != 0u) || (b + 1u == nb && (uint64_t)f1 != total);
+  }
+  if (bad) {                                     // (workgroup-uniform)
+    if (tid == 0) atomicOr(status, ZN_DEV_CORRUPT);
+    return;
+  }
+  const uint16_t* off = (const uint16_t*)(p + zn_patch_a1(nb));
+  const T* val = (const T*)(p + zn_patch_a2(nb, total));
+  T* dst = (T*)ZN_GLOBAL_PTR(uint8_t, sg.dst);
+  const uint64_t e_lo = sg.byte_lo / E, e_hi = sg.byte_hi / E, blk0 = (uint64_t)b * ZN_PATCH_BLOCK;
+  bool wrong = false;
+  for (uint32_t i = f0 + tid; i < f1; i += ZN_PA_THREADS) {
+    const uint32_t o = off[i];
+    const T v = val[i];
+    const uint64_t el = blk0 + o;
+    if (el >= m || v == (T)0 || (i > f0 && (uint32_t)off[i - 1u] >= o)) { wrong = true; continue; }
+    if (el >= e_lo && el < e_hi) dst[el - e_lo] ^= v;
+  }
+  if (wrong) atomicOr(status, ZN_DEV_CORRUPT);
+}
+
+__global__ void __launch_bounds__(ZN_PA_THREADS) zn_k_patch_apply(const ZnPatchASeg one, const ZnPatchASeg* __restrict__ segs_, uint32_t nseg, uint32_t* __restrict__ status) {
+  const ZnPatchASeg* segs = ZN_GLOBAL_PTR(const ZnPatchASeg, segs_);
+  const ZnPatchASeg sg = zn_pa_find(one, segs, nseg, blockIdx.x);
+  const uint32_t b = sg.b_lo + (blockIdx.x - sg.wg0);
+  if (sg.E == 1u) zn_pa_apply_block<1>(sg, b, status);
+  else if (sg.E == 2u) zn_pa_apply_block<2>(sg, b, status);
+  else zn_pa_apply_block<4>(sg, b, status);
+}
+
+void zn_launch_patch_count(const ZnPatchBSeg& one, const ZnPatchBSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_words, hipStream_t stream) {
+  if (nseg == 0 || total_wg == 0) return;
+  hipLaunchKernelGGL(zn_k_patch_count, dim3(total_wg), dim3(ZN_PA_THREADS), 0, stream, one, d_segs, nseg, d_words);
+  zn_note_kernel("zn_k_patch_count");
+}
+void zn_launch_patch_scan(const ZnPatchBSeg& one, const ZnPatchBSeg* d_segs, uint32_t nseg, uint32_t* d_words, uint64_t* d_totals, hipStream_t stream) {
+  if (nseg == 0) return;
+  hipLaunchKernelGGL(zn_k_patch_scan, dim3(nseg), dim3(ZN_PA_THREADS), 0, stream, one, d_segs, d_words, d_totals);
+  zn_note_kernel("zn_k_patch_scan");
+}
+void zn_launch_patch_emit(const ZnPatchBSeg& one, const ZnPatchBSeg* d_segs, uint32_t nseg, uint32_t total_wg, const uint32_t* d_words, hipStream_t stream) {
+  if (nseg == 0 || total_wg == 0) return;
+  hipLaunchKernelGGL(zn_k_patch_emit, dim3(total_wg), dim3(ZN_PA_THREADS), 0, stream, one, d_segs, nseg, const_cast<uint32_t*>(d_words));
+  zn_note_kernel("zn_k_patch_emit");
+}
+void zn_launch_patch_apply(const ZnPatchASeg& one, const ZnPatchASeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_status, hipStream_t stream) {
+  if (nseg == 0 || total_wg == 0) return;
+  hipLaunchKernelGGL(zn_k_patch_apply, dim3(total_wg), dim3(ZN_PA_THREADS), 0, stream, one, d_segs, nseg, d_status);
+  zn_note_kernel("zn_k_patch_apply");
+}
+
+// ---- the C ABI of the patches (host side: checks, tables, launches) ----
+namespace {
+
+bool patch_elem_ok(size_t n, int elem) { return (elem == 1 || elem == 2 || elem == 4) && n % (size_t)elem == 0 && (uint64_t)(n / (size_t)elem) < (1ull << 32); }
+bool patch_aligned(const void* p, int elem) { return (((uintptr_t)p) & (uintptr_t)(elem - 1)) == 0; }
+
+// a table of `count` entries of S through the pinned staging buffer into WS_SEGS at byte offset `at`; the caller has synchronised with the buffer's last reader
+template <typename S>
+int patch_stage(Workspace& w, const std::vector<S>& segs, size_t at, hipStream_t stream) {
+  const size_t bytes = segs.size() * sizeof(S);
+  memcpy((uint8_t*)w.h_segs.p + at, segs.data(), bytes);
+  ZN_HIP(hipMemcpyAsync((uint8_t*)w.buf[WS_SEGS] + at, (uint8_t*)w.h_segs.p + at, bytes, hipMemcpyHostToDevice, stream));
+  return ZN_OK;
+}
+
+// Count, scan, one read-back of every item's T; with `emit`: capacity check, then the emit pass for the items that differ.  Synchronous.
+struct PatchSrc { const void* d_src; const void* d_base; size_t n; int elem; void* d_patch; size_t cap; };
+int patch_build(const std::vector<PatchSrc>& items, std::vector<uint64_t>& lens, bool emit, hipStream_t stream) {
+  const size_t count = items.size();
+  lens.assign(count, 0);
+  if (count == 0) return ZN_OK;
+  if (count > 0x7FFFFFFFull) return ZN_E_ARG;
+  std::vector<ZnPatchBSeg> segs(count);
+  uint64_t wg = 0, words = 0;
+  for (size_t i = 0; i < count; i++) {
+    const PatchSrc& it = items[i];
+    if (!patch_elem_ok(it.n, it.elem)) return ZN_E_ARG;
+    if (it.n && (!it.d_src || !it.d_base || !patch_aligned(it.d_src, it.elem) || !patch_aligned(it.d_base, it.elem))) return ZN_E_ARG;
+    if (emit && it.cap && (!it.d_patch || (((uintptr_t)it.d_patch) & 15u) != 0)) return ZN_E_ARG;
+    const uint64_t m = it.n / (size_t)it.elem;
+    segs[i] = ZnPatchBSeg{(const uint8_t*)it.d_src, (const uint8_t*)it.d_base, (uint8_t*)it.d_patch, m, (uint32_t)wg, (uint32_t)words, (uint32_t)it.elem, 0u};
+    wg += zn_patch_blocks(m); words += zn_patch_blocks(m) + 1u;
+    if (wg > 0x7FFFFFFFull || words > 0x7FFFFFFFull) return ZN_E_ARG;
+  }
+  WsLease L;
+  if (L.rc) return L.rc;
+  Workspace& w = *L.w;
+  t_kernels.clear();
+  int rc;
+  const bool table = count > 1;
+  const size_t table_bytes = table ? count * sizeof(ZnPatchBSeg) : 0u;          // (twice: the emit pass has a grid of its own)
+  if ((rc = w.reserve(WS_META_A, words * sizeof(uint32_t)))) return rc;
+  if ((rc = w.reserve(WS_TOTALS, count * sizeof(uint64_t)))) return rc;
+  if ((rc = w.h_totals.reserve(count * sizeof(uint64_t)))) return rc;
+  if (table && (rc = w.reserve(WS_SEGS, 2u * table_bytes))) return rc;
+  if ((rc = L.acquire(stream))) return rc;
+  L.mark = table;
+  if (table) {
+    ZN_HIP(hipEventSynchronize(w.busy));         // the previous batched call may still be reading the pinned staging
+    if ((rc = w.h_segs.reserve(2u * table_bytes))) return rc;
+    if ((rc = patch_stage(w, segs, 0, stream))) return rc;
+  }
+  const ZnPatchBSeg* d_segs = table ? (const ZnPatchBSeg*)w.buf[WS_SEGS] : nullptr;
+  uint32_t* d_words = (uint32_t*)w.buf[WS_META_A];
+  uint64_t* d_totals = (uint64_t*)w.buf[WS_TOTALS];
+  zn_launch_patch_count(segs[0], d_segs, (uint32_t)count, (uint32_t)wg, d_words, stream);
+  zn_launch_patch_scan(segs[0], d_segs, (uint32_t)count, d_words, d_totals, stream);
+  if (launch_failed()) return ZN_E_HIP;
+  ZN_HIP(hipMemcpyAsync(w.h_totals.p, d_totals, count * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  ZN_HIP(hipStreamSynchronize(stream));
+  const uint64_t* T = (const uint64_t*)w.h_totals.p;
+  bool short_cap = false;
+  for (size_t i = 0; i < count; i++) {
+    lens[i] = T[i] ? zn_patch_total(segs[i].m, segs[i].E, T[i]) : 0u;           // (0: the tensor's bytes are the base's)
+    if (emit && lens[i] > items[i].cap) short_cap = true;
+  }
+  if (!emit) return ZN_OK;
+  if (short_cap) return ZN_E_CAP;
+  uint64_t ewg = 0;
+  for (size_t i = 0; i < count; i++) { segs[i].wg0 = (uint32_t)ewg; if (T[i]) ewg += zn_patch_blocks(segs[i].m); }
+  if (ewg == 0) return ZN_OK;
+  // (the first table's copy is over — the stream was synchronised —; the emit table goes behind it)
+  if (table && (rc = patch_stage(w, segs, table_bytes, stream))) return rc;
+  zn_launch_patch_emit(segs[0], table ? (const ZnPatchBSeg*)((const uint8_t*)w.buf[WS_SEGS] + table_bytes) : nullptr, (uint32_t)count, (uint32_t)ewg, d_words, stream);
+  if (launch_failed()) return ZN_E_HIP;
+  ZN_HIP(hipStreamSynchronize(stream));
+  return ZN_OK;
+}
+
+// what an apply call or plan works out before its first launch
+struct PatchApplySet {
+  std::vector<ZnPatchASeg> segs;
+  struct Copy { void* dst; const void* src; size_t n; };
+  std::vector<Copy> copies;                      // items with d_base: the window's bytes of the base go to the destination first
+  uint64_t total_wg = 0;
+};
+int patch_apply_segments(const zn_patch_apply_item* items, size_t count, PatchApplySet& A) {
+  if (count && !items) return ZN_E_ARG;
+  if (count > 0x7FFFFFFFull) return ZN_E_ARG;
+  A.segs.resize(count);
+  for (size_t i = 0; i < count; i++) {
+    const zn_patch_apply_item& it = items[i];
+    if (!patch_elem_ok(it.n, it.elem)) return ZN_E_ARG;
+    const size_t E = (size_t)it.elem;
+    if (!it.d_patch || (((uintptr_t)it.d_patch) & 15u) != 0 || it.patch_len < 32u) return ZN_E_ARG;
+    if (it.byte_lo > it.byte_hi || it.byte_hi > it.n || it.byte_lo % E || it.byte_hi % E) return ZN_E_ARG;
+    const bool empty = it.byte_lo == it.byte_hi;
+    if (!empty && (!it.d_dst || !patch_aligned(it.d_dst, it.elem))) return ZN_E_ARG;
+    const uint64_t b_lo = (it.byte_lo / E) / ZN_PATCH_BLOCK, b_hi = empty ? b_lo : zn_patch_blocks(it.byte_hi / E);
+    A.segs[i] = ZnPatchASeg{(const uint8_t*)it.d_patch, it.patch_len, it.n, (uint8_t*)it.d_dst, it.byte_lo, it.byte_hi, (uint32_t)A.total_wg, (uint32_t)it.elem, (uint32_t)b_lo, 0u};
+    A.total_wg += b_hi - b_lo;
+    if (A.total_wg > 0x7FFFFFFFull) return ZN_E_ARG;
+    if (!empty && it.d_base) A.copies.push_back({it.d_dst, (const uint8_t*)it.d_base + it.byte_lo, it.byte_hi - it.byte_lo});
+  }
+  return ZN_OK;
+}
+
+// the launches of an apply: d_table null = the table is staged through the pinned buffer (or, for one item, travels as the kernel's argument)
+int patch_apply_launch(const PatchApplySet& A, const ZnPatchASeg* d_table, hipStream_t stream, int check) {
+  if (A.total_wg == 0 && A.copies.empty()) return ZN_OK;
+  WsLease L;
+  if (L.rc) return L.rc;
+  Workspace& w = *L.w;
+  t_kernels.clear();
+  int rc;
+  const bool staged = A.segs.size() > 1 && !d_table && A.total_wg;
+  const size_t table_bytes = A.segs.size() * sizeof(ZnPatchASeg);
+  if ((rc = w.reserve(WS_WORDS, ZN_WORDS_BYTES))) return rc;
+  if ((rc = w.host_words())) return rc;
+  if (staged && (rc = w.reserve(WS_SEGS, table_bytes))) return rc;
+  if ((rc = L.acquire(stream))) return rc;
+  L.mark = staged;
+  bool chain;
+  uint32_t* d_status = zn_take_status_slot(w, L.dev, check, &chain);
+  if (!chain) ZN_HIP(hipMemsetAsync(d_status, 0, 4 * sizeof(uint32_t), stream));      // (chained: the status word is the sequence's)
+  for (const PatchApplySet::Copy& c : A.copies)
+    if (c.dst != c.src) ZN_HIP(hipMemcpyAsync(c.dst, c.src, c.n, hipMemcpyDeviceToDevice, stream));
+  if (staged) {
+    ZN_HIP(hipEventSynchronize(w.busy));         // the previous batched call may still be reading the pinned staging
+    if ((rc = w.h_segs.reserve(table_bytes))) return rc;
+    if ((rc = patch_stage(w, A.segs, 0, stream))) return rc;
+    d_table = (const ZnPatchASeg*)w.buf[WS_SEGS];
+  }
+  if (A.total_wg) zn_launch_patch_apply(A.segs[0], A.segs.size() > 1 ? d_table : nullptr, (uint32_t)A.segs.size(), (uint32_t)A.total_wg, d_status, stream);
+  if (launch_failed()) return ZN_E_HIP;
+  if (check) {
+    ZN_HIP(hipMemcpyAsync(w.h_status, d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    ZN_HIP(hipStreamSynchronize(stream));
+    return status_to_rc(*w.h_status);
+  }
+  return ZN_OK;
+}
+
+}  // namespace
+
+// A prepared apply: the segments, the base copies, and the table in device memory of its own (zn_plan's counterpart for patches).
+struct zn_patch_plan {
+  PatchApplySet A;
+  ZnPatchASeg* d_table = nullptr;
+  hipEvent_t last = nullptr;
+  bool ran = false;
+  int dev = 0;
+  ~zn_patch_plan() {
+    if (d_table) (void)hipFree(d_table);
+    if (last) (void)hipEventDestroy(last);
+  }
+};
+
+extern "C" {
+
+size_t zn_patch_len(size_t n, int elem, size_t entries) {
+  if (!patch_elem_ok(n, elem) || entries > n / (size_t)elem) return 0;
+  return (size_t)zn_patch_total(n / (size_t)elem, (uint32_t)elem, entries);
+}
+
+int zn_patch_size_batch_dev(const zn_patch_size_item* items, size_t count, size_t* sizes_out, void* stream_) {
+  try {
+    if (count == 0) return ZN_OK;
+    if (!items || !sizes_out) return ZN_E_ARG;
+    std::vector<PatchSrc> src(count);
+    for (size_t i = 0; i < count; i++) src[i] = PatchSrc{items[i].d_src, items[i].d_base, items[i].n, items[i].elem, nullptr, 0};
+    std::vector<uint64_t> lens;
+    const int rc = patch_build(src, lens, false, (hipStream_t)stream_);
+    if (rc) return rc;
+    for (size_t i = 0; i < count; i++) sizes_out[i] = (size_t)lens[i];
+    return ZN_OK;
+  } catch (...) { return ZN_E_ALLOC; }
+}
+
+int zn_patch_build_batch_dev(zn_patch_build_item* items, size_t count, void* stream_) {
+  try {
+    if (count == 0) return ZN_OK;
+    if (!items) return ZN_E_ARG;
+    std::vector<PatchSrc> src(count);
+    for (size_t i = 0; i < count; i++) { src[i] = PatchSrc{items[i].d_src, items[i].d_base, items[i].n, items[i].elem, items[i].d_patch, items[i].patch_cap}; items[i].patch_len = 0; }
+    std::vector<uint64_t> lens;
+    const int rc = patch_build(src, lens, true, (hipStream_t)stream_);
+    if (rc == ZN_OK || rc == ZN_E_CAP) for (size_t i = 0; i < count; i++) items[i].patch_len = (size_t)lens[i];      // (ZN_E_CAP: the lengths that were needed; nothing was written)
+    return rc;
+  } catch (...) { return ZN_E_ALLOC; }
+}
+
+int zn_patch_apply_batch_dev(const zn_patch_apply_item* items, size_t count, void* stream_, int check) {
+  try {
+    PatchApplySet A;
+    const int rc = patch_apply_segments(items, count, A);
+    return rc ? rc : patch_apply_launch(A, nullptr, (hipStream_t)stream_, check);
+  } catch (...) { return ZN_E_ALLOC; }
+}
+
+int zn_patch_plan_create(const zn_patch_apply_item* items, size_t count, zn_patch_plan** plan) {
+  if (!plan) return ZN_E_ARG;
+  *plan = nullptr;
+  try {
+    int dev = 0, rc = zn_current_dev(&dev);
+    if (rc) return rc;
+    std::unique_ptr<zn_patch_plan> pl(new zn_patch_plan());
+    pl->dev = dev;
+    if ((rc = patch_apply_segments(items, count, pl->A))) return rc;
+    if (pl->A.segs.size() > 1) {
+      const size_t bytes = pl->A.segs.size() * sizeof(ZnPatchASeg);
+      hipError_t e = hipMalloc((void**)&pl->d_table, bytes);
+      if (e != hipSuccess) { pl->d_table = nullptr; t_hip_err = std::string("hipMalloc: ") + hipGetErrorString(e); (void)hipGetLastError(); return ZN_E_ALLOC; }
+      ZN_HIP(hipMemcpy(pl->d_table, pl->A.segs.data(), bytes, hipMemcpyHostToDevice));
+    }
+    ZN_HIP(hipEventCreateWithFlags(&pl->last, hipEventDisableTiming));
+    *plan = pl.release();
+    return ZN_OK;
+  } catch (...) { return ZN_E_ALLOC; }
+}
+
+int zn_patch_plan_run(zn_patch_plan* plan, void* stream_, int check) {
+  if (!plan) return ZN_E_ARG;
+  try {
+    int dev = 0;
+    ZN_HIP(hipGetDevice(&dev));
+    if (dev != plan->dev) return ZN_E_ARG;
+    const int rc = patch_apply_launch(plan->A, plan->d_table, (hipStream_t)stream_, check);
+    if (plan->d_table) { if (hipEventRecord(plan->last, (hipStream_t)stream_) == hipSuccess) plan->ran = true; else { (void)hipGetLastError(); (void)hipDeviceSynchronize(); } }
+    return rc;
+  } catch (...) { return ZN_E_ALLOC; }
+}
+
+int zn_patch_plan_destroy(zn_patch_plan* plan) {
+  if (!plan) return ZN_OK;
+  int rc = ZN_OK;
+  {
+    DeviceScope scope(plan->dev);
+    if (!scope.ok || (plan->ran && hipEventSynchronize(plan->last) != hipSuccess)) { t_hip_err = "zn_patch_plan_destroy"; (void)hipGetLastError(); (void)hipDeviceSynchronize(); rc = ZN_E_HIP; }
+    delete plan;
+  }
+  return rc;
+}
+
+}  // extern "C"

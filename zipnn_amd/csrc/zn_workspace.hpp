@@ -200,5 +200,9 @@ static inline int pipe_copy(ZnHostPipe& p, void* d, const void* h, size_t n, boo
   return ZN_E_HIP;
 }
 
+// The status slot of a call that reports the way decodes do (zn_api.hip: a new slot, or — zn_decode_status_chain — the slot of the thread's previous unchecked
+// call, *chain then true: its status word is kept).  The caller holds the device's WsLease and has reserved WS_WORDS.
+uint32_t* zn_take_status_slot(Workspace& w, int dev, int check, bool* chain);
+
 // zn_release_workspace's part of zn_api_host.hip: the host staging of the multi-device compress calls
 void zn_host_release_stage();

@@ -33,6 +33,19 @@ def _numel(shape):
     return n
 
 
+def _patch_entries(n, elem, length):
+    """-> T of a "znp1" patch of `length` bytes for a tensor of n bytes, elem bytes per element (include/zipnn_hip.h: L = round16(A1 + 2 T) + elem T, which
+    grows strictly with T)."""
+    nb = (n // elem + 65535) // 65536
+    a1 = (32 + 4 * (nb + 1) + 15) // 16 * 16
+    t = max((length - a1) // (2 + elem) - 16, 0)
+    while (a1 + 2 * t + 15) // 16 * 16 + elem * t < length:
+        t += 1
+    if (a1 + 2 * t + 15) // 16 * 16 + elem * t != length:
+        raise ValueError(f"{length} is not the length of a patch of a tensor of {n} bytes")
+    return t
+
+
 def _stream_of(dev, stream=None):
     """-> the raw stream handle to launch on: `stream` (a torch.cuda.Stream or a handle), else the device's current stream."""
     if stream is not None:
@@ -60,8 +73,11 @@ class _Entry:
     In a variant store (ResidentCheckpoint.from_state_dict(..., base=...)): `delta` is True where the body encodes tensor ^ base, "same" where the tensor's
     bytes are the base's (no body; `raw` is the base's own tensor where the base holds it plainly) and False otherwise; `base` is what a delta or "same" entry
     decodes over and `restore` what revert_ puts back — ("tensor", the base's tensor, held by reference) or ("entry", the base store, its entry) — or None.
-    `head`: the first 16 bytes of the frame header the body was written behind or would be (magic … dtype code): what save_file writes in front of it again."""
-    __slots__ = ("name", "dtype", "shape", "nbytes", "body", "raw", "P", "bits", "byts", "chunk", "hints", "delta", "base", "restore", "head")
+    `head`: the first 16 bytes of the frame header the body was written behind or would be (magic … dtype code): what save_file writes in front of it again.
+    A SPARSE entry (from_state_dict(..., base=..., sparse=True)): `delta` is "sparse", there is no body, `patch` is the "znp1" patch
+    (include/zipnn_hip.h) that turns the base's bytes into the tensor's and `entries` its number of elements; reading it is the base's bytes with the patch
+    XORed in.  Its frame parameters are those the tensor would be coded with: windows are counted in their chunks."""
+    __slots__ = ("name", "dtype", "shape", "nbytes", "body", "raw", "P", "bits", "byts", "chunk", "hints", "delta", "base", "restore", "head", "patch", "entries")
 
     def __init__(self, name, dtype, shape, nbytes, body=None, raw=None, params=None):
         self.name, self.dtype, self.shape, self.nbytes, self.body, self.raw = name, dtype, tuple(int(d) for d in shape), int(nbytes), body, raw
@@ -69,6 +85,7 @@ class _Entry:
         self.P, self.bits, self.byts, self.chunk = params if params is not None else (0, 0, 0, 0)
         self.delta, self.base, self.restore = False, None, None
         self.head = None
+        self.patch, self.entries = None, 0
 
     @property
     def compressed(self):
@@ -77,7 +94,7 @@ class _Entry:
     @property
     def decoded(self):
         """Whether reading the tensor runs a decode (a body of its own, or a "same" entry over a base that is compressed itself)."""
-        return self.body is not None or (self.delta == "same" and self.raw is None)
+        return self.body is not None or self.patch is not None or (self.delta == "same" and self.raw is None)
 
     @property
     def chunks(self):
@@ -93,6 +110,12 @@ class _Entry:
         h = self.hints
         item = (self.window(lo, hi, dst_ptr, delta_ptr), h.data_ptr() if h is not None else None, h.numel() if h is not None else 0)
         return item + (_capi.HINT_DELTA,) if delta_ptr is not None else item
+
+    def patch_item(self, lo, hi, dst_ptr, base_ptr=None):
+        """-> the item tuple of ZnLib.patch_apply_batch_dev / patch_plan_create for chunks [lo, hi) of this sparse entry: the patch's entries inside that byte
+        window XORed into dst_ptr — over what lies there, or (base_ptr: the WHOLE tensor's base) over a copy of the base's window."""
+        item = (self.patch.data_ptr(), self.patch.numel(), self.nbytes, self.P, lo * self.chunk, min(hi * self.chunk, self.nbytes), dst_ptr)
+        return item + (base_ptr,) if base_ptr is not None else item
 
     def view(self, flat):
         """flat uint8 bytes of the whole tensor -> the tensor."""
@@ -120,6 +143,8 @@ class ResidentCheckpoint:
         ft.apply_(model)          # tensors that hold the base's values now hold the fine-tune's, in place (XOR is its own inverse) …
         ft.revert_(model)         # … and the base's again
         ft.info(n)["delta"]       # True, False or "same"
+        ft = ResidentCheckpoint.from_state_dict(ft_sd, "cuda:0", base=base, sparse=True)      # tensors with few changed elements are kept as "znp1" patches
+        ft.info(n)["delta"], ft.info(n)["patch_entries"]                                          # "sparse", the number of elements that differ
 
     CONTENT DIGESTS ("zn64-1"; an error-detecting code, not a cryptographic hash) let a store answer whether what it decodes is still what it was built from:
 
@@ -320,7 +345,7 @@ class ResidentCheckpoint:
     _BUILD_GROUP_BYTES = 1 << 30
 
     @classmethod
-    def from_state_dict(cls, sd, device="cuda:0", threshold=0.95, method=None, index=False, base=None, digests=False):
+    def from_state_dict(cls, sd, device="cuda:0", threshold=0.95, method=None, index=False, base=None, digests=False, sparse=False):
         """Compress the tensors of a state dict on `device` (one batched call) and keep the bodies, trimmed to their lengths and packed at
         256-byte boundaries of one allocation.  A tensor whose body would not be smaller than the tensor itself — and every tensor the codec
         does not take: integers, float64, empty ones — is kept as it is.  index=True: build_index() on the new store; index="deltas":
@@ -334,6 +359,10 @@ class ResidentCheckpoint:
         on a tie; a tensor whose bytes ARE the base's is recorded as "same" and holds nothing.  Decodes combine delta and base on the way out; the
         variant keeps its base alive.  Plain base tensors are held BY REFERENCE and read at decode time: the caller keeps them at the base's values
         (apply_ on those very tensors changes what the variant decodes over until revert_).  resident_bytes counts the variant's own memory.
+        sparse=True (with base): a delta candidate is also COUNTED against its base — one pass, no bytes written — and where the "znp1" patch (the changed
+        elements with their XOR values, include/zipnn_hip.h) would be smaller than the best body so far it is built and kept instead:
+        info(name)["delta"] == "sparse".  The smallest of plain body, delta body and patch wins, ties in that order, so nothing that is chosen without
+        `sparse` changes.  Every read path serves such an entry (the base's bytes, then the patch applied in place); save_file does not yet.
         Peak memory of the build, beside `sd` on the device: the plain pass's compress arena (as large as the tensors, as without `base`); then the
         plain bodies and, as they come, the delta bodies — each a trimmed copy out of its arena —, plus per group of at most 1 GiB of tensors (or one
         larger tensor) the decoded tensors of a resident base and one arena of the group's size; at the end the kept bodies are copied once more into
@@ -391,7 +420,7 @@ class ResidentCheckpoint:
                 plain = trimmed(codec.compress_device_batch(lib, [(codec.flat_bytes(t), P, bits, byts, chunk, float(threshold)) for (_, t, (P, bits, byts, chunk)) in todo]))
                 refs = [matches(name, t) for (name, t, _) in todo]
                 cand = [i for i, ((name, t, prm), ref) in enumerate(zip(todo, refs)) if ref is not None and delta_ok(ref, t, prm)]
-                dbody, same = {}, set()
+                dbody, same, pbody = {}, set(), {}
                 # in groups of at most _BUILD_GROUP_BYTES of base bytes: plain base tensors are read where they lie, a resident base's tensors are decoded
                 # a group at a time (never the whole base at once), the group's "is it the base's bytes" flags come back in one read
                 groups, cur, size = [], [], 0
@@ -414,6 +443,13 @@ class ResidentCheckpoint:
                     if rest:
                         got = trimmed(codec.compress_device_batch(lib, [(codec.flat_bytes(todo[i][1]),) + tuple(todo[i][2]) + (float(threshold), flats[i]) for i in rest]))
                         dbody.update(zip(rest, got))
+                    if sparse and rest:                # the count pass gives every patch's length; only those below the best body so far are built
+                        elig = [i for i in rest if codec.patch_elem(todo[i][1]) == todo[i][2][0]]
+                        pairs = [(codec.flat_bytes(todo[i][1]), flats[i], todo[i][2][0]) for i in elig]
+                        sizes = codec.patch_sizes_device_batch(lib, pairs)
+                        take = [k for k, i in enumerate(elig) if 0 < sizes[k] < min(plain[i].numel(), dbody[i].numel(), flats[i].numel())]
+                        built = codec.patch_build_device_batch(lib, [pairs[k] for k in take], [sizes[k] for k in take])
+                        pbody.update({elig[k]: b.clone() for k, b in zip(take, built)})
                     del flats, decoded
             kept = []                              # (index, body, is a delta body)
             for i, (name, t, prm) in enumerate(todo):
@@ -422,6 +458,8 @@ class ResidentCheckpoint:
                 b, is_delta = plain[i], False
                 if i in dbody and dbody[i].numel() < b.numel():        # (a tie goes to the plain body)
                     b, is_delta = dbody[i], True
+                if i in pbody and pbody[i].numel() < min(b.numel(), t.numel() * t.element_size()):      # (… and the patch only when it is smaller than either)
+                    b, is_delta = pbody[i], "sparse"
                 if b.numel() < t.numel() * t.element_size():
                     kept.append((i, b, is_delta))
             offs, o = [], 0
@@ -432,6 +470,11 @@ class ResidentCheckpoint:
             for (i, b, is_delta), off in zip(kept, offs):
                 name, t, prm = todo[i]
                 packed[off:off + b.numel()].copy_(b)
+                if is_delta == "sparse":
+                    e = entries[name] = _Entry(name, t.dtype, t.shape, t.numel() * t.element_size(), params=prm)
+                    e.patch, e.delta, e.base = packed[off:off + b.numel()], "sparse", refs[i]
+                    e.entries = _patch_entries(e.nbytes, e.P, b.numel())
+                    continue
                 e = entries[name] = _Entry(name, t.dtype, t.shape, t.numel() * t.element_size(), body=packed[off:off + b.numel()], params=prm)
                 if is_delta:
                     e.delta, e.base = True, refs[i]
@@ -446,11 +489,11 @@ class ResidentCheckpoint:
                 entries[name].restore = ref
             keep.append(packed)
             held += o
-            del plain, dbody                   # (the bodies not kept go back to the allocator)
+            del plain, dbody, pbody            # (the bodies not kept go back to the allocator)
         for name, t in sd.items():
             if entries[name].restore is None:
                 entries[name].restore = matches(name, t.detach())
-        held += sum(e.nbytes for e in entries.values() if not e.compressed and e.delta != "same")
+        held += sum(e.nbytes for e in entries.values() if not e.compressed and e.delta not in ("same", "sparse"))
         if base is not None:
             keep.append(base)
         for name, h in heads.items():
@@ -522,16 +565,29 @@ class ResidentCheckpoint:
         must run on one stream: [("hinted" | "window", items)].  A plain entry: one window item.  A delta entry over a plain base tensor: the item with
         d_delta at that tensor (the library offsets it to the window).  Over a resident base: the BASE's own sets decode the same chunk window into the
         destination first — hinted if the base has an index, through its own base if it is a variant itself — and the delta's window then runs IN PLACE over
-        it (d_dst == d_delta + chunk_lo * chunk, include/zipnn_hip.h).  A "same" entry is the base's decode alone.  keep: a list that receives what
-        the items refer to by address."""
+        it (d_dst == d_delta + chunk_lo * chunk, include/zipnn_hip.h).  A "same" entry is the base's decode alone.  A SPARSE entry adds a third kind of set,
+        ("patch", items of zn_patch_apply_batch_dev), behind the others: over a plain base tensor the item has d_base at that tensor (the window's bytes are
+        copied, then patched); over a resident base the base's own sets decode the window into the destination — hinted where it has an index, through its own
+        patches if it is a sparse variant itself — and the patch's window is applied in place.  keep: a list that receives what the items refer to by address."""
         keep = keep if keep is not None else []
 
         def ptr(dst):                              # (a destination may also be given by its address)
             return dst if isinstance(dst, int) else dst.data_ptr()
-        via, plain, delta = {}, [], []                 # (delta: (entry, lo, hi, destination address, base address))
+        via, plain, delta, patch = {}, [], [], []      # (delta: (entry, lo, hi, destination address, base address); patch: items of the apply call)
         for e, lo, hi, dst in work:
             if e.delta is False:
                 plain.append((e, lo, hi, dst))
+                continue
+            if e.delta == "sparse":
+                keep.append(e.patch)
+                if e.base[0] == "tensor":
+                    bt = codec.flat_bytes(e.base[1])
+                    keep.append(bt)
+                    patch.append(e.patch_item(lo, hi, ptr(dst), bt.data_ptr()))
+                else:
+                    _, bstore, be = e.base
+                    via.setdefault(id(bstore), (bstore, []))[1].append((be, lo, hi, dst))
+                    patch.append(e.patch_item(lo, hi, ptr(dst)))
                 continue
             if e.base[0] == "tensor":                  # (a delta entry: "same" over a plain tensor is that tensor, never work)
                 bt = codec.flat_bytes(e.base[1])
@@ -552,6 +608,8 @@ class ResidentCheckpoint:
             else:
                 sets.append(("window", [e.window(lo, hi, ptr(dst)) for e, lo, hi, dst in plain]))
         sets += self._delta_sets(delta, keep)
+        if patch:
+            sets.append(("patch", patch))
         keep += [dst for _, _, _, dst in work if not isinstance(dst, int)]
         return sets
 
@@ -579,6 +637,8 @@ class ResidentCheckpoint:
                         lib.decode_status_chain(True)
                     if kind == "hinted":
                         lib.decompress_hinted_batch_dev(items, stream, check)
+                    elif kind == "patch":
+                        lib.patch_apply_batch_dev(items, stream, check)
                     else:
                         lib.decompress_window_batch_dev(items, stream, check)
             finally:
@@ -602,8 +662,9 @@ class ResidentCheckpoint:
 
     def info(self, name):
         e = self._entries[name]
-        return {"shape": list(e.shape), "dtype": e.dtype, "nbytes": e.nbytes, "compressed": e.compressed, "delta": e.delta,
-                "resident_bytes": e.body.numel() if e.compressed else (0 if e.delta == "same" else e.nbytes),
+        return {"shape": list(e.shape), "dtype": e.dtype, "nbytes": e.nbytes, "compressed": e.compressed or e.patch is not None, "delta": e.delta,
+                "resident_bytes": e.body.numel() if e.compressed else e.patch.numel() if e.patch is not None else (0 if e.delta == "same" else e.nbytes),
+                "patch_entries": e.entries if e.patch is not None else None,
                 "index_bytes": e.hints.numel() if e.hints is not None else 0,
                 "digest": self._digests[name] if self._digests is not None else None}
 
@@ -645,10 +706,14 @@ class ResidentCheckpoint:
         from_file(path, device, base=...) / safetensors_io.load_file(path, device, base=...).
         digests: None writes `znn_digests` when the store has digests; True computes them (one decode of every tensor) where it has none; False omits them.
         metadata: the file's other metadata (default: what from_file found in the store's own file, else {"format": "pt"}).  The sync index is not saved:
-        from_file(index=True) rebuilds it."""
+        from_file(index=True) rebuilds it.  A store with SPARSE entries is refused (ValueError naming them): patches have no file form yet."""
         from safetensors.torch import save_file as st_save_file
         from . import safetensors_io
         lib = _capi.lib()
+        sparse = [e.name for e in self._entries.values() if e.patch is not None]
+        if sparse:
+            raise ValueError(f"save_file: the file format has no form for sparse entries yet (DESIGN §3.10): {', '.join(repr(n) for n in sparse[:8])}{' …' if len(sparse) > 8 else ''}"
+                             " — build the store without sparse=True to write it down")
         recorded = None
         if digests or (digests is None and self._digests is not None):
             recorded = self._digests if self._digests is not None else self._decoded_digests(self.keys())
@@ -894,40 +959,45 @@ class ResidentCheckpoint:
     def apply_(self, target, check=True, guard=False):
         """Turn live BASE weights into the fine-tune's, in place: `target` is a module or a mapping of names to contiguous tensors on the store's device that
         hold the base's values.  Delta entries are XORed over them by an in-place decode (d_dst == d_delta, include/zipnn_hip.h) — no second copy of the
-        weights, no read of the base —, plain entries are overwritten, "same" entries are left alone; one batched launch set on the current stream.
+        weights, no read of the base —, sparse entries are their patch applied in place (zn_patch_apply_batch_dev alone: only the changed elements are touched),
+        plain entries are overwritten, "same" entries are left alone; one batched launch set on the current stream.
         Nothing is tracked: applying twice (or to tensors that do not hold the base) XORs the delta in twice and is the caller's mistake — unless guard=True
         (a store with digests): the live tensors are digested first and must hold the BASE's values, else DigestMismatch is raised before anything is touched.  If `target` is
         the very tensors this store holds as its plain base, the store decodes wrong values until revert_.  -> the names changed."""
         if guard:
             self._guard(target, True)
-        work, inplace, done = [], [], []
+        work, inplace, done, patch = [], [], [], []
         for e, t in self._targets(target):
             if e.delta == "same" or not e.nbytes:
                 continue
             if e.delta is True:
                 inplace.append((e, 0, e.chunks, t.data_ptr(), t.data_ptr()))
+            elif e.delta == "sparse":
+                patch.append(e.patch_item(0, e.chunks, t.data_ptr()))
             elif e.compressed:
                 work.append((e, 0, e.chunks, codec.flat_bytes(t)))
             else:
                 t.copy_(e.raw)
             done.append(e.name)
-        sets = self._launch_sets(work) + self._delta_sets(inplace)
+        sets = self._launch_sets(work) + self._delta_sets(inplace) + ([("patch", patch)] if patch else [])
         self._run_sets(sets, check)
         return done
 
     def revert_(self, target, check=True, guard=False):
-        """The inverse of apply_: delta entries by the same in-place call again (XOR is its own inverse), plain entries restored from the base — its
+        """The inverse of apply_: delta and sparse entries by the same in-place call again (XOR is its own inverse), plain entries restored from the base — its
         tensor copied, or its resident body decoded — where the base has the tensor with the same dtype and shape.  -> the names that could NOT be
         reverted (plain entries with nothing to restore from: they stay as they are).  Reverting what was not applied is the caller's mistake — unless
         guard=True (a store with digests): the live tensors must hold THIS store's values, else DigestMismatch is raised before anything is touched."""
         if guard:
             self._guard(target, False)
-        work, inplace, stay, via = [], [], [], {}
+        work, inplace, stay, via, patch = [], [], [], {}, []
         for e, t in self._targets(target):
             if e.delta == "same" or not e.nbytes:
                 continue
             if e.delta is True:
                 inplace.append((e, 0, e.chunks, t.data_ptr(), t.data_ptr()))
+            elif e.delta == "sparse":
+                patch.append(e.patch_item(0, e.chunks, t.data_ptr()))
             elif e.restore is None:
                 stay.append(e.name)
             elif e.restore[0] == "tensor":
@@ -941,7 +1011,7 @@ class ResidentCheckpoint:
         sets = []
         for bstore, w in via.values():
             sets += bstore._launch_sets(w)
-        sets += self._delta_sets(inplace)
+        sets += self._delta_sets(inplace) + ([("patch", patch)] if patch else [])
         self._run_sets(sets, check)
         return stay
 
@@ -995,7 +1065,8 @@ class ResidentPlan:
     of the next layer can be enqueued while this one still runs.  `tensors` are the views the runs fill; `status()` waits and raises what a
     checked decode would have raised; `close()` frees the plan (the store must outlive it).  The plan of a variant store over a resident base holds
     zn_plans of its own and of its base — the base's decode, then the delta windows in place over it —, launched back to back; their verdicts are
-    chained (zn_decode_status_chain), so `status()` speaks for the whole run."""
+    chained (zn_decode_status_chain), so `status()` speaks for the whole run.  Sparse entries add a patch plan (zn_patch_plan) behind them: its table lives
+    on the device too, and its run is launches only."""
 
     def __init__(self, store, names, into=None):
         self._store, self._lib = store, _capi.lib()
@@ -1010,10 +1081,12 @@ class ResidentPlan:
             hs = []
             try:
                 for kind, items in (sets or [("window", [])]):
-                    hs.append(self._lib.plan_create_hinted(items) if kind == "hinted" else self._lib.plan_create(items))
+                    if kind == "patch":
+                        hs.append((True, self._lib.patch_plan_create(items)))
+                    else:
+                        hs.append((False, self._lib.plan_create_hinted(items) if kind == "hinted" else self._lib.plan_create(items)))
             except Exception:
-                for h in hs:
-                    self._lib.plan_destroy(h)
+                self._destroy(hs)
                 raise
             self._hs = hs
 
@@ -1023,10 +1096,13 @@ class ResidentPlan:
         self._stream = _stream_of(self._store.device, stream)
         with _device_of(self._store.device):
             try:
-                for i, h in enumerate(self._hs):
+                for i, (is_patch, h) in enumerate(self._hs):
                     if i == 1:
                         self._lib.decode_status_chain(True)       # (the later plans add their verdict to the first one's: status() speaks for the whole run)
-                    self._lib.plan_run(h, self._stream, False)
+                    if is_patch:
+                        self._lib.patch_plan_run(h, self._stream, False)
+                    else:
+                        self._lib.plan_run(h, self._stream, False)
             finally:
                 if len(self._hs) > 1:
                     self._lib.decode_status_chain(False)
@@ -1036,11 +1112,17 @@ class ResidentPlan:
         with _device_of(self._store.device):
             self._lib.decode_status(self._stream if self._stream is not None else _stream_of(self._store.device))
 
+    def _destroy(self, hs):
+        for is_patch, h in hs:
+            if is_patch:
+                self._lib.patch_plan_destroy(h)
+            else:
+                self._lib.plan_destroy(h)
+
     def close(self):
         if self._hs is not None:
             hs, self._hs = self._hs, None
-            for h in hs:
-                self._lib.plan_destroy(h)
+            self._destroy(hs)
 
     def __del__(self):
         try:
