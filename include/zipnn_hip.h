@@ -324,7 +324,25 @@ int zn_digest_host(const void* src, size_t n, unsigned long long* out);
  *   block, or a zero value.  (first[] is checked for the blocks the window touches.)  A wrong patch costs the verdict, never a byte outside the destination;
  *   the destination itself is then undefined.
  * zn_patch_plan_*: mirror zn_plan_*: the table lives in device memory the plan owns, a run launches only (and enqueues the base copies of items with d_base), its
- *   verdict joins a chain when the thread has one open; the plan refers to patches, destinations and bases by address. */
+ *   verdict joins a chain when the thread has one open; the plan refers to patches, destinations and bases by address.
+ * zn_patch_check_batch_dev: is each patch WELL-FORMED — the whole of it, before anything is applied?  What a reader does with a patch it did not build itself (a
+ *   file's): apply checks only what its window reads and has written by the time it knows.  One launch for the batch (zn_k_patch_check: one workgroup
+ *   per block of every item), which reads [d_patch, d_patch + patch_len) and writes nothing but the verdict words; synchronous, one read-back for the batch, like
+ *   zn_patch_size_batch_dev.  verdicts_out[i] (host) = 0 for a well-formed patch of a tensor of n bytes in elements of `elem`, else a mask of
+ *     ZN_PATCH_BAD_HEADER   the magic, E or n is not the item's, T > m, or L is not patch_len and the formula's value for T (nothing else is read then)
+ *     ZN_PATCH_BAD_FIRST    first[0] != 0, first[NB] != T, or a pair first[b] > first[b + 1] or first[b + 1] > T — every pair, not a window's
+ *     ZN_PATCH_BAD_OFFSET   an offset at or beyond the tensor's last element, or offsets not strictly ascending inside a block
+ *     ZN_PATCH_BAD_VALUE    a zero value
+ *     ZN_PATCH_BAD_PADDING  the canonical form, which apply never reads: header bytes 5-7, the bytes between first[] and off[] or between off[] and val[] not zero
+ *   entries_out[i] (host, may be NULL) = T of a well-formed item, 0 otherwise.  The call returns ZN_OK whenever it ran — the verdicts are per item —, ZN_E_ARG before
+ *   any launch for patch_len < 32, a d_patch that is null or not 16-byte aligned, or an (n, elem) that is not eligible.
+ *   What it cannot see: a first[] boundary moved so that both neighbouring blocks still ascend is a well-formed patch — of another tensor.  Only the content
+ *   digests (verify) catch that. */
+#define ZN_PATCH_BAD_HEADER 1u
+#define ZN_PATCH_BAD_FIRST 2u
+#define ZN_PATCH_BAD_OFFSET 4u
+#define ZN_PATCH_BAD_VALUE 8u
+#define ZN_PATCH_BAD_PADDING 16u
 typedef struct zn_patch_size_item { const void* d_src; const void* d_base; size_t n; int elem; } zn_patch_size_item;
 typedef struct zn_patch_build_item {
   const void* d_src; const void* d_base; size_t n; int elem;
@@ -345,6 +363,11 @@ int zn_patch_apply_batch_dev(const zn_patch_apply_item* items, size_t count, voi
 int zn_patch_plan_create(const zn_patch_apply_item* items, size_t count, zn_patch_plan** plan);
 int zn_patch_plan_run(zn_patch_plan* plan, void* stream, int check);
 int zn_patch_plan_destroy(zn_patch_plan* plan);
+typedef struct zn_patch_check_item { const void* d_patch; size_t patch_len; size_t n; int elem; } zn_patch_check_item;
+int zn_patch_check_batch_dev(const zn_patch_check_item* items, size_t count,
+                             unsigned int* verdicts_out,        /* host, one per item: 0 = well-formed */
+                             unsigned long long* entries_out,   /* host, may be NULL: T of each well-formed item */
+                             void* stream);
 
 /* Plumbing for callers that keep the tensors in HBM but hold pageable host buffers (files, Python bytes): the same
  * pinned, multi-threaded transfer the host-buffer entry points above use internally (zipnn_amd/csrc/zn_host_pipe.hpp),

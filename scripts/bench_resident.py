@@ -34,6 +34,8 @@ blocks of leg b as the base, the two fine-tunes of --delta:
 --delta-index: the sync index of variant stores instead (build_index(deltas=True), DESIGN §3.6 "Two kinds"), into profiles/resident_delta_index.{json,txt}:
   p  per fine-tune of --delta: plan.run of one block from a variant over a resident indexed base, without and with the variant's DELTA index, interleaved in
      both orders (A B A B B A B A: the four runs without are the A/A spread), the build time of the DELTA index and its size
+--sparse-file: sparse variants written down and read back (save_file(sparse=True), from_file(check_patches=)), into profiles/resident_sparse_file.{json,txt}:
+  f  file bytes against the delta and the plain file; from_file with and without the patch check; the check call against a device copy; plan.run loaded against built
 --sparse: sparse variant stores instead (from_state_dict(..., base=..., sparse=True)), into profiles/resident_sparse.{json,txt}:
   s  per fine-tune of --delta, over a resident indexed base: resident bytes and build time without and with sparse=True; plan.run of one block from either
      store, interleaved in both orders (A B A B B A B A: the four runs of the delta store are the A/A spread); apply_ + revert_ of one block from either
@@ -759,6 +761,102 @@ def main_sparse(args):
     return 0
 
 
+def leg_f(args):
+    """--sparse-file: the sparse variants of --sparse written by save_file(sparse=True) and read back: file bytes against the delta file and the
+    plain file and against Σ (L + 15); from_file with check_patches True against False, interleaved; the check call alone against a device copy of the same
+    bytes; plan.run of one block from the loaded store against the built one, interleaved in both orders."""
+    import tempfile
+    import torch
+    from zipnn_amd import ResidentCheckpoint, _capi, codec
+    sd, per = _blocks(args.layers)
+    names = per[0]
+    res = {"layers": args.layers, "fine_tunes": []}
+    base = ResidentCheckpoint.from_state_dict(sd, "cuda:0", index=True)
+
+    def wall(fn):
+        torch.cuda.synchronize(); t0 = time.perf_counter(); r = fn(); torch.cuda.synchronize()
+        return r, (time.perf_counter() - t0) * 1e3
+    with tempfile.TemporaryDirectory() as td:
+        for kind in ("sparse", "drift"):
+            ft = _fine_tune(sd, kind, 21)
+            sp = ResidentCheckpoint.from_state_dict(ft, "cuda:0", base=base, sparse=True)
+            files = {"sparse": sp.save_file(os.path.join(td, f"{kind}.sparse.znn.safetensors"), sparse=True),
+                     "delta": ResidentCheckpoint.from_state_dict(ft, "cuda:0", base=base).save_file(os.path.join(td, f"{kind}.delta.znn.safetensors")),
+                     "plain": ResidentCheckpoint.from_state_dict(ft, "cuda:0").save_file(os.path.join(td, f"{kind}.plain.znn.safetensors"))}
+            patches = [k for k in ft if sp.info(k)["delta"] == "sparse"]
+            r = {"kind": kind, "tensors": len(ft), "nbytes": sp.nbytes, "sparse_entries": len(patches), "file_bytes": {k: os.path.getsize(v) for k, v in files.items()},
+                 "entries_sum": sum(sp.info(k)["resident_bytes"] + 15 for k in patches), "patch_bytes": sum(sp.info(k)["resident_bytes"] for k in patches)}
+            load = {True: [], False: []}
+            for flag in (True, False, True, False, False, True, False, True, True, False):
+                st, ms = wall(lambda: ResidentCheckpoint.from_file(files["sparse"], "cuda:0", base=base, check_patches=flag))
+                load[flag].append(ms)
+                del st
+            r["from_file_ms"] = {"checked": sorted(load[True])[len(load[True]) // 2], "unchecked": sorted(load[False])[len(load[False]) // 2], "all": {str(k): v for k, v in load.items()}}
+            loaded = ResidentCheckpoint.from_file(files["sparse"], "cuda:0", base=base)
+            for k in ft:
+                assert sp.info(k)["delta"] == loaded.info(k)["delta"] and sp.info(k)["resident_bytes"] == loaded.info(k)["resident_bytes"], k
+            if patches:
+                lib = _capi.lib()
+                items = [(loaded._entries[k].patch, loaded._entries[k].nbytes, loaded._entries[k].P) for k in patches]
+                calls = sorted(wall(lambda: codec.patch_check_device_batch(lib, items))[1] for _ in range(args.reps))
+                r["check_call_ms"] = calls[len(calls) // 2]
+                # (the call is synchronous: the events below enclose its launch, read-back and sync as well as the kernel)
+                src = torch.empty(r["patch_bytes"], dtype=torch.uint8, device="cuda"); dst = torch.empty_like(src)
+                r["copy_same_bytes_ms"] = _events_ms(lambda: dst.copy_(src), args.reps)["median_ms"]
+                r["check_events_ms"] = _events_ms(lambda: codec.patch_check_device_batch(lib, items), args.reps)["median_ms"]
+                r["addresses_mod_256"] = sorted({loaded._entries[k].patch.data_ptr() % 256 for k in patches})
+                scratch = torch.empty(sp.scratch_bytes(names), dtype=torch.uint8, device="cuda")
+                runs = {"built": [], "loaded": []}
+                stores = {"built": sp, "loaded": loaded}
+                for leg in ("built", "loaded", "built", "loaded", "loaded", "built", "loaded", "built"):
+                    plan = stores[leg].plan(names, into=scratch)
+                    t = _events_ms(plan.run, args.reps)
+                    plan.status()
+                    for k in names:
+                        assert _same(plan.tensors[k], ft[k]), (kind, leg, k)
+                    runs[leg].append(t["median_ms"])
+                    plan.close()
+                r["plan_run_ms"] = runs
+                a = runs["built"]
+                r["aa_spread"] = (max(a) - min(a)) / min(a)
+            res["fine_tunes"].append(r)
+            del sp, loaded, ft
+            torch.cuda.empty_cache()
+    return res
+
+
+def main_sparse_file(args):
+    p = subprocess.run(["timeout", "-k", "10", "540", sys.executable, os.path.abspath(__file__), "--leg", "f", "--layers", str(args.layers), "--reps", str(args.reps)],
+                       capture_output=True, text=True)
+    line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+    if p.returncode != 0 or not line:
+        print(f"leg f failed (exit {p.returncode})\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}")
+        return 1
+    res = json.loads(line[0][7:])
+    out = args.out if args.out != os.path.join(ROOT, "profiles", "resident_decode") else os.path.join(ROOT, "profiles", "resident_sparse_file")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    lines = [f"command: python scripts/bench_resident.py --sparse-file --layers {args.layers} --reps {args.reps}",
+             "sparse file probe (save_file(sparse=True) / from_file(base=, check_patches=), DESIGN §3.11): the fine-tunes of --sparse over a resident indexed base; walls are",
+             "host perf_counter between device syncs (median of 5 per setting, interleaved), plan.run and the copy are device events (median ms); every result checked"]
+    for r in res["fine_tunes"]:
+        f = r["file_bytes"]
+        lines.append(f"  {r['kind']:<7} {r['sparse_entries']} of {r['tensors']} tensors sparse: file {f['sparse']} B against the delta file {f['delta']} B = {f['sparse'] / f['delta']:.3f}, the plain file {f['plain']} B"
+                     f" = {f['sparse'] / f['plain']:.3f}, {f['sparse'] / r['nbytes']:.4f} of the raw bytes; sparse entries {r['entries_sum']} B = Σ (L + 15)")
+        q = r["from_file_ms"]
+        lines.append(f"          from_file wall: check_patches=True {q['checked']:.3f} ms, False {q['unchecked']:.3f} ms" + (f"; the check call alone {r['check_call_ms']:.4f} ms wall"
+                     f" = {100 * r['check_call_ms'] / q['checked']:.1f} % of the checked load" if "check_call_ms" in r else ""))
+        if "plan_run_ms" in r:
+            lines.append(f"          check call between device events {r['check_events_ms']:.4f} ms (launch, read-back and sync included) against a device copy of the same {r['patch_bytes']} B: {r['copy_same_bytes_ms']:.4f} ms"
+                         f" = {r['check_events_ms'] / r['copy_same_bytes_ms']:.2f} x")
+            p_ = r["plan_run_ms"]
+            lines.append("          plan.run built " + " / ".join(f"{x:.4f}" for x in p_["built"]) + "   loaded " + " / ".join(f"{x:.4f}" for x in p_["loaded"]) +
+                         f"   (A/A spread of the built runs: {100 * r['aa_spread']:.1f} %; loaded patches at addresses mod 256: {r['addresses_mod_256']})")
+    open(out + ".txt", "w").write("\n".join(lines) + "\n")
+    json.dump(res, open(out + ".json", "w"), indent=1)
+    print("\n".join(lines))
+    return 0
+
+
 def main_index(args):
     results = {}
     for leg, limit in INDEX_LEG_SECONDS.items():
@@ -801,6 +899,7 @@ def main():
     ap.add_argument("--delta-file", action="store_true", help="the delta file leg (n) instead of a-e")
     ap.add_argument("--delta-index", action="store_true", help="the DELTA sync index leg (p) instead of a-e")
     ap.add_argument("--sparse", action="store_true", help="the sparse variant leg (s) instead of a-e")
+    ap.add_argument("--sparse-file", action="store_true", help="the sparse file leg (f) instead of a-e")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resident_decode"))
     args = ap.parse_args()
     if args.leg:                                          # a child: one leg, its result as one JSON line
@@ -818,6 +917,8 @@ def main():
         return main_delta_index(args)
     if args.sparse:
         return main_sparse(args)
+    if args.sparse_file:
+        return main_sparse_file(args)
     results = {}
     for leg, limit in LEG_SECONDS.items():
         p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--layers", str(args.layers), "--reps", str(args.reps)],

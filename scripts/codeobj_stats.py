@@ -35,7 +35,8 @@ HOT = [("zn_k_decode_fusedILi1ELb0ELb0E", "decode_fused<1> plain"), ("zn_k_decod
        ("zn_k_encode_statsILi2ELb0E", "encode_stats<2>"), ("zn_k_encode_emitILi2ELb0E", "encode_emit<2>"), ("zn_k_encode_onepassILi2ELb0E", "encode_onepass<2>"),
        ("zn_k_encode_tables", "encode_tables"),
        ("11zn_k_digest8", "digest (zn64-1, §3.8)"), ("16zn_k_digest_init", "digest_init"),
-       ("zn_k_patch_count", "patch_count (znp1, §3.10)"), ("zn_k_patch_scan", "patch_scan"), ("zn_k_patch_emit", "patch_emit"), ("zn_k_patch_apply", "patch_apply")]
+       ("zn_k_patch_count", "patch_count (znp1, §3.10)"), ("zn_k_patch_scan", "patch_scan"), ("zn_k_patch_emit", "patch_emit"), ("zn_k_patch_apply", "patch_apply"),
+       ("zn_k_patch_check", "patch_check (§3.11)")]
 
 
 def kernels_of(obj):

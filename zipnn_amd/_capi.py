@@ -101,6 +101,15 @@ class ZnPatchApplyItem(ctypes.Structure):
 assert ctypes.sizeof(ZnPatchApplyItem) == 64
 
 
+class ZnPatchCheckItem(ctypes.Structure):
+    """struct zn_patch_check_item of include/zipnn_hip.h"""
+    _fields_ = [("d_patch", ctypes.c_void_p), ("patch_len", ctypes.c_size_t), ("n", ctypes.c_size_t), ("elem", ctypes.c_int)]
+
+
+# the bits of a zn_patch_check_batch_dev verdict
+PATCH_BAD_HEADER, PATCH_BAD_FIRST, PATCH_BAD_OFFSET, PATCH_BAD_VALUE, PATCH_BAD_PADDING = 1, 2, 4, 8, 16
+
+
 class ZnLib:
     """A loaded libzipnn_hip.so."""
 
@@ -212,6 +221,9 @@ class ZnLib:
             L.zn_patch_plan_run.argtypes = [vp, vp, ci]
             L.zn_patch_plan_destroy.restype = ci
             L.zn_patch_plan_destroy.argtypes = [vp]
+        if hasattr(L, "zn_patch_check_batch_dev"):      # (likewise: a library from before the check)
+            L.zn_patch_check_batch_dev.restype = ci
+            L.zn_patch_check_batch_dev.argtypes = [ctypes.POINTER(ZnPatchCheckItem), sz, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_ulonglong), vp]
         L.zn_copy_to_device.restype = ci; L.zn_copy_to_device.argtypes = [vp, vp, sz]
         L.zn_copy_to_host.restype = ci; L.zn_copy_to_host.argtypes = [vp, vp, sz]
         L.zn_release_workspace.restype = ci
@@ -640,6 +652,18 @@ class ZnLib:
 
     def patch_plan_destroy(self, plan):
         self._check(self._L.zn_patch_plan_destroy(plan))
+
+    def patch_check_batch_dev(self, items, stream=0):
+        """zn_patch_check_batch_dev.  items: iterable of (patch_ptr, patch_len, n, elem) -> ([verdict mask per item: 0 = well-formed, else PATCH_BAD_* bits],
+        [T per item: 0 where the verdict is not 0]); one launch, one read-back."""
+        items = list(items)
+        arr = (ZnPatchCheckItem * max(len(items), 1))()
+        for i, (pp, pl, n, el) in enumerate(items):
+            arr[i].d_patch = pp or None; arr[i].patch_len = pl; arr[i].n = n; arr[i].elem = el
+        verdicts = (ctypes.c_uint * max(len(items), 1))()
+        entries = (ctypes.c_ulonglong * max(len(items), 1))()
+        self._check(self._L.zn_patch_check_batch_dev(arr, len(items), verdicts, entries, ctypes.c_void_p(stream or None)))
+        return [int(verdicts[i]) for i in range(len(items))], [int(entries[i]) for i in range(len(items))]
 
     def decode_status(self, stream=0):
         """zn_decode_status: wait for `stream`, raise what the last check=False decode call on this device would have raised."""

@@ -319,6 +319,50 @@ def patch_apply_(t, patch, check=True):
     return t
 
 
+PATCH_BAD_NAMES = ((1, "header"), (2, "first"), (4, "offset"), (8, "value"), (16, "padding"))      # the ZN_PATCH_BAD_* bits of a check verdict
+
+
+def patch_verdict_text(mask):
+    """A zn_patch_check_batch_dev verdict in words: 'offset+value (0x0c)'."""
+    return "+".join(name for bit, name in PATCH_BAD_NAMES if mask & bit) + f" (0x{mask:02x})"
+
+
+def patch_check_device_batch(lib, items, stream=None):
+    """items: [(patch: a contiguous uint8 tensor at a 16-byte aligned address, n: the tensor's bytes, elem)] on one device -> ([verdict mask], [T]) by ONE
+    zn_patch_check_batch_dev launch and one read-back: are the patches well-formed, the whole of each, for tensors of those sizes?  Nothing is written."""
+    items = list(items)
+    if not items:
+        return [], []
+    for p, _, _ in items:
+        if p.dtype != torch.uint8 or not p.is_contiguous() or p.device != items[0][0].device:
+            raise ValueError("patch: contiguous uint8 tensors on one device")
+    dev = items[0][0].device
+    with torch.cuda.device(dev) if dev.type == "cuda" else _nullctx():
+        return lib.patch_check_batch_dev([(p.data_ptr(), p.numel(), n, el) for p, n, el in items], stream if stream is not None else _stream_handle(items[0][0]))
+
+
+def patch_check(patch, t):
+    """Is `patch` a well-formed "znp1" patch (include/zipnn_hip.h) for tensor `t` — what patch_build gives for a tensor of t's dtype and size?  Every field, every
+    first[] pair, every entry and the padding are checked on the device, read-only, before anything is applied (patch_apply_ checks as it goes, and has written by
+    then).  -> T, the number of elements the patch changes; a malformed patch raises ZnError(ZN_E_CORRUPT) whose `mask` holds the ZN_PATCH_BAD_* bits.  None
+    (identical tensors) -> 0.  Well-formed is not RIGHT: a patch of another tensor of the same size passes; content digests tell those apart."""
+    from . import _capi
+    if patch is None:
+        return 0
+    d = t.detach()
+    el = patch_elem(d)
+    if el is None:
+        raise ValueError("patch_check: a tensor with elements of 1, 2 or 4 bytes, fewer than 2^32 of them")
+    if patch.dtype != torch.uint8 or patch.device != d.device or not patch.is_contiguous():
+        raise ValueError("patch_check: the patch is a contiguous uint8 tensor on the tensor's device")
+    verdicts, entries = patch_check_device_batch(_capi.lib(), [(patch, d.numel() * el, el)])
+    if verdicts[0]:
+        err = _capi.ZnError(_capi.ZN_E_CORRUPT, f"patch_check: the patch is malformed: {patch_verdict_text(verdicts[0])}")
+        err.mask = verdicts[0]
+        raise err
+    return entries[0]
+
+
 # ---- content digests ("zn64-1": include/zipnn_hip.h, DESIGN §3.8) -------------------------------------------------------------------------
 DIGEST_ALGO = "zn64-1"
 

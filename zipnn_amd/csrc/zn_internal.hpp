@@ -162,6 +162,10 @@ void zn_launch_patch_count(const ZnPatchBSeg& one, const ZnPatchBSeg* d_segs, ui
 void zn_launch_patch_scan(const ZnPatchBSeg& one, const ZnPatchBSeg* d_segs, uint32_t nseg, uint32_t* d_words, uint64_t* d_totals, hipStream_t stream);    // d_totals[i] = T of item i
 void zn_launch_patch_emit(const ZnPatchBSeg& one, const ZnPatchBSeg* d_segs, uint32_t nseg, uint32_t total_wg, const uint32_t* d_words, hipStream_t stream);
 void zn_launch_patch_apply(const ZnPatchASeg& one, const ZnPatchASeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_status, hipStream_t stream);
+// One item of a check launch (zn_k_patch_check): the patch and the tensor it claims to describe; its first workgroup — one per block, one for a tensor without
+// elements — and its slot of the launch's verdict words: d_words[2 slot] collects the ZN_PATCH_BAD_* bits, d_words[2 slot + 1] receives the header's T.
+struct ZnPatchCSeg { const uint8_t* patch; uint64_t patch_len; uint64_t n; uint32_t wg0; uint32_t E; uint32_t slot; uint32_t pad_; };
+void zn_launch_patch_check(const ZnPatchCSeg& one, const ZnPatchCSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_words, hipStream_t stream);
 
 // kernel-name log for zn_last_kernels()
 void zn_note_kernel(const char* name);

@@ -4,6 +4,7 @@
 //   zn_k_patch_scan    one workgroup per item: the block counts become first[] (an exclusive prefix sum, in place), the item's T goes to its total
 //   zn_k_patch_emit    one workgroup per block again: off / val of the block's differing elements at first[b] + rank, in ascending order; block 0 writes the header
 //   zn_k_patch_apply   one workgroup per block of the window: dst[e] ^= val for the block's entries inside the window, after checking everything it reads
+//   zn_k_patch_check   one workgroup per block of the tensor: the whole patch against the format, read-only — a mask of findings per item
 //
 // Count and emit are ONE body (zn_pa_block<E, EMIT>): the same loads, the same comparison, the same order of elements.  The emit instance never writes outside
 // [first[b], first[b + 1]) of off / val: if the source changed between the two passes the patch is wrong, not the memory around it.  A thread takes 16 consecutive
@@ -227,6 +228,82 @@ __global__ void __launch_bounds__(ZN_PA_THREADS) zn_k_patch_apply(const ZnPatchA
   else zn_pa_apply_block<4>(sg, b, status);
 }
 
+// ---- zn_k_patch_check: is the WHOLE patch well-formed?  Apply's checks restated (zn_pa_apply_block stays what it is) for every block and every entry, and the
+// canonical form apply never reads.  Reads [patch, patch + patch_len) — the header first, which bounds every later index, as in apply — and writes verdict words.
+// A thread takes 8 consecutive entries per step: one 16-byte load of off[] (groups start at multiples of 8 entries; off[] is padded to a multiple of 16 bytes, so
+// a group that holds an entry lies inside the patch) and the 8 E bytes of val[] in 8- or 16-byte loads where all 8 are entries (val[] has no padding behind it).
+struct alignas(16) ZnPcOffs { uint16_t o[8]; };
+template <uint32_t E> struct alignas(E == 1u ? 8 : 16) ZnPcVals { typename ZnPaElem<E>::t v[8]; };
+
+template <uint32_t E>
+__device__ __forceinline__ void zn_pc_block(const ZnPatchCSeg& sg, uint32_t b, uint32_t* __restrict__ words) {
+  typedef typename ZnPaElem<E>::t T;
+  const uint32_t tid = threadIdx.x;
+  const uint8_t* p = ZN_GLOBAL_PTR(const uint8_t, sg.patch);
+  uint32_t* verdict = words + 2u * sg.slot;
+  const uint64_t n = sg.n, m = n / E, nb = zn_patch_blocks(m);                   // (the host has checked: n % E == 0, m < 2^32, patch_len >= 32, b < max(nb, 1))
+  const uint32_t magic = *(const uint32_t*)p, e = p[4];
+  const uint64_t hn = *(const uint64_t*)(p + 8), total = *(const uint64_t*)(p + 16), len = *(const uint64_t*)(p + 24);
+  bool bad = magic != ZN_PATCH_MAGIC || e != E || hn != n || total > m || len != sg.patch_len;
+  if (!bad) bad = zn_patch_total(m, E, total) != len;
+  if (bad) {                                     // (workgroup-uniform) nothing behind the header is read
+    if (tid == 0) atomicOr(verdict, ZN_PATCH_BAD_HEADER);
+    return;
+  }
+  const uint64_t a1 = zn_patch_a1(nb), a2 = zn_patch_a2(nb, total);
+  uint32_t found = 0;
+  if (b == 0) {                                  // the item's T, and the canonical form: three runs of fewer than 16 bytes
+    if (tid == 0) verdict[1] = (uint32_t)total;  // (total <= m < 2^32)
+    if (tid < 16u) {
+      const uint64_t i1 = 32u + 4u * (nb + 1u) + tid, i2 = a1 + 2u * total + tid;
+      if ((tid >= 5u && tid < 8u && p[tid]) || (i1 < a1 && p[i1]) || (i2 < a2 && p[i2])) found |= ZN_PATCH_BAD_PADDING;
+    }
+  }
+  const uint32_t* first = (const uint32_t*)(p + 32);
+  const uint32_t f0 = first[b], f1 = nb ? first[b + 1u] : f0;                    // (a tensor without elements: first[0] alone, and T == 0)
+  if (f0 > f1 || (uint64_t)f1 > total || (b == 0 && f0 != 0u) || ((uint64_t)b + 1u >= nb && (uint64_t)f1 != total)) found |= ZN_PATCH_BAD_FIRST;      // (workgroup-uniform)
+  else {
+    const uint16_t* off = (const uint16_t*)(p + a1);
+    const T* val = (const T*)(p + a2);
+    const uint64_t blk0 = (uint64_t)b * ZN_PATCH_BLOCK;
+    for (uint64_t g = (uint64_t)(f0 & ~7u) + 8u * tid; g < f1; g += 8u * ZN_PA_THREADS) {
+      const ZnPcOffs og = *(const ZnPcOffs*)(off + g);
+      ZnPcVals<E> vg;
+      if (g + 8u <= total) vg = *(const ZnPcVals<E>*)(val + g);
+      else {
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; k++) vg.v[k] = g + k < total ? val[g + k] : (T)1;
+      }
+      bool have = g > f0;                        // is there an entry of this block in front of the one looked at?
+      uint32_t prev = have ? (uint32_t)off[g - 1u] : 0u;
+#pragma unroll
+      for (uint32_t k = 0; k < 8u; k++) {
+        const uint64_t i = g + k;
+        if (i < f0) continue;
+        const uint32_t o = og.o[k];
+        if (i < f1) {
+          if (blk0 + o >= m || (have && prev >= o)) found |= ZN_PATCH_BAD_OFFSET;
+          if (vg.v[k] == (T)0) found |= ZN_PATCH_BAD_VALUE;
+        }
+        prev = o; have = true;
+      }
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) found |= __shfl_xor(found, d);
+  if ((tid & 63u) == 0 && found) atomicOr(verdict, found);                       // (at most one per wave)
+}
+
+__global__ void __launch_bounds__(ZN_PA_THREADS) zn_k_patch_check(const ZnPatchCSeg one, const ZnPatchCSeg* __restrict__ segs_, uint32_t nseg, uint32_t* __restrict__ words_) {
+  const ZnPatchCSeg* segs = ZN_GLOBAL_PTR(const ZnPatchCSeg, segs_);
+  const ZnPatchCSeg sg = zn_pa_find(one, segs, nseg, blockIdx.x);
+  uint32_t* words = ZN_GLOBAL_PTR(uint32_t, words_);
+  const uint32_t b = blockIdx.x - sg.wg0;
+  if (sg.E == 1u) zn_pc_block<1>(sg, b, words);
+  else if (sg.E == 2u) zn_pc_block<2>(sg, b, words);
+  else zn_pc_block<4>(sg, b, words);
+}
+
 void zn_launch_patch_count(const ZnPatchBSeg& one, const ZnPatchBSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_words, hipStream_t stream) {
   if (nseg == 0 || total_wg == 0) return;
   hipLaunchKernelGGL(zn_k_patch_count, dim3(total_wg), dim3(ZN_PA_THREADS), 0, stream, one, d_segs, nseg, d_words);
@@ -246,6 +323,11 @@ void zn_launch_patch_apply(const ZnPatchASeg& one, const ZnPatchASeg* d_segs, ui
   if (nseg == 0 || total_wg == 0) return;
   hipLaunchKernelGGL(zn_k_patch_apply, dim3(total_wg), dim3(ZN_PA_THREADS), 0, stream, one, d_segs, nseg, d_status);
   zn_note_kernel("zn_k_patch_apply");
+}
+void zn_launch_patch_check(const ZnPatchCSeg& one, const ZnPatchCSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_words, hipStream_t stream) {
+  if (nseg == 0 || total_wg == 0) return;
+  hipLaunchKernelGGL(zn_k_patch_check, dim3(total_wg), dim3(ZN_PA_THREADS), 0, stream, one, d_segs, nseg, d_words);
+  zn_note_kernel("zn_k_patch_check");
 }
 
 // ---- the C ABI of the patches (host side: checks, tables, launches) ----
@@ -445,6 +527,54 @@ int zn_patch_apply_batch_dev(const zn_patch_apply_item* items, size_t count, voi
     PatchApplySet A;
     const int rc = patch_apply_segments(items, count, A);
     return rc ? rc : patch_apply_launch(A, nullptr, (hipStream_t)stream_, check);
+  } catch (...) { return ZN_E_ALLOC; }
+}
+
+int zn_patch_check_batch_dev(const zn_patch_check_item* items, size_t count, unsigned int* verdicts_out, unsigned long long* entries_out, void* stream_) {
+  try {
+    if (count == 0) return ZN_OK;
+    if (!items || !verdicts_out || count > 0x7FFFFFFFull) return ZN_E_ARG;
+    hipStream_t stream = (hipStream_t)stream_;
+    std::vector<ZnPatchCSeg> segs(count);
+    uint64_t wg = 0;
+    for (size_t i = 0; i < count; i++) {
+      const zn_patch_check_item& it = items[i];
+      if (!patch_elem_ok(it.n, it.elem)) return ZN_E_ARG;
+      if (!it.d_patch || (((uintptr_t)it.d_patch) & 15u) != 0 || it.patch_len < 32u) return ZN_E_ARG;
+      const uint64_t nb = zn_patch_blocks(it.n / (size_t)it.elem);
+      segs[i] = ZnPatchCSeg{(const uint8_t*)it.d_patch, it.patch_len, it.n, (uint32_t)wg, (uint32_t)it.elem, (uint32_t)i, 0u};
+      wg += nb ? nb : 1u;                        // (a tensor without elements still has a header and first[0])
+      if (wg > 0x7FFFFFFFull) return ZN_E_ARG;
+    }
+    WsLease L;
+    if (L.rc) return L.rc;
+    Workspace& w = *L.w;
+    t_kernels.clear();
+    int rc;
+    const bool table = count > 1;
+    const size_t table_bytes = table ? count * sizeof(ZnPatchCSeg) : 0u, word_bytes = count * 2u * sizeof(uint32_t);
+    if ((rc = w.reserve(WS_TOTALS, word_bytes))) return rc;
+    if ((rc = w.h_totals.reserve(word_bytes))) return rc;
+    if (table && (rc = w.reserve(WS_SEGS, table_bytes))) return rc;
+    if ((rc = L.acquire(stream))) return rc;
+    L.mark = table;
+    uint32_t* d_words = (uint32_t*)w.buf[WS_TOTALS];
+    ZN_HIP(hipMemsetAsync(d_words, 0, word_bytes, stream));
+    if (table) {
+      ZN_HIP(hipEventSynchronize(w.busy));       // the previous batched call may still be reading the pinned staging
+      if ((rc = w.h_segs.reserve(table_bytes))) return rc;
+      if ((rc = patch_stage(w, segs, 0, stream))) return rc;
+    }
+    zn_launch_patch_check(segs[0], table ? (const ZnPatchCSeg*)w.buf[WS_SEGS] : nullptr, (uint32_t)count, (uint32_t)wg, d_words, stream);
+    if (launch_failed()) return ZN_E_HIP;
+    ZN_HIP(hipMemcpyAsync(w.h_totals.p, d_words, word_bytes, hipMemcpyDeviceToHost, stream));
+    ZN_HIP(hipStreamSynchronize(stream));
+    const uint32_t* got = (const uint32_t*)w.h_totals.p;
+    for (size_t i = 0; i < count; i++) {
+      verdicts_out[i] = got[2u * i];
+      if (entries_out) entries_out[i] = got[2u * i] ? 0ull : (unsigned long long)got[2u * i + 1u];
+    }
+    return ZN_OK;
   } catch (...) { return ZN_E_ALLOC; }
 }
 

@@ -178,7 +178,7 @@ class ResidentCheckpoint:
         return dev
 
     @classmethod
-    def from_file(cls, path, device="cuda:0", index=False, digests=False, verify=False, base=None, verify_base=True):
+    def from_file(cls, path, device="cuda:0", index=False, digests=False, verify=False, base=None, verify_base=True, check_patches=True):
         """A `.znn.safetensors` file (this library's or the reference's): its data section goes to `device` once, in one transfer, and stays.
         index=True: build_index() on the new store; index="deltas": build_index(deltas=True) — the delta bodies of a delta file get their index too.
         digests=True: the store records a content digest per tensor (digests(), verify(), holds()).  A file written with digests
@@ -195,7 +195,15 @@ class ResidentCheckpoint:
         with verify_base=True (the default) the base's digests are compared with the file's `base_digests` before anything is uploaded or decoded: a base
         store's recorded digests are used as they are, a base without them is digested once, all its needed tensors in one batch (decoded, or where they lie);
         DigestMismatch names the tensors that differ.  verify=True keeps its meaning: the decoded fine-tune against `znn_digests`.  A file that is no delta file
-        takes `base` only as what revert_ restores from."""
+        takes `base` only as what revert_ restores from.
+        SPARSE entries (a file written by save_file(sparse=True)) become what from_state_dict(..., sparse=True) holds: the patch a 16-byte aligned
+        view of the uploaded data section, info(n)["delta"] == "sparse".  A patch from a file is one this process did not build, so it is refused BY NAME AT LOAD
+        instead of by the first apply that reads its damage (apply_ on live weights has written by then): before the upload every sparse entry's header is read
+        from the file — a ValueError names the tensor whose entry is not the header's L + 15 bytes long, whose magic, element size or n is not its dtype's and
+        shape's, or whose L is not zn_patch_len of its T — and with check_patches=True (the default) the slack around every patch must be zero and, after the
+        upload and before anything is decoded, ONE zn_patch_check_batch_dev call validates every patch whole (header, first[], every entry, padding); a ValueError
+        names every damaged tensor with its mask.  check_patches=False skips both; apply's own checks remain.  A well-formed patch of ANOTHER tensor passes:
+        verify=True (the digests) is what catches that."""
         import json
         from . import safetensors_io
         dev = cls._work_device(device)
@@ -207,7 +215,7 @@ class ResidentCheckpoint:
         if delta is not None and base is None:
             raise safetensors_io._needs_base(path)
         based = cls._base_items(base, dev)
-        kinds, over = {}, {}                                           # {name: "delta" | "same"}, {name: (dtype, shape, what it is coded over)}
+        kinds, over = {}, {}                                           # {name: "delta" | "same" | "sparse"}, {name: (dtype, shape, what it is coded over)}
         if delta is not None:
             kinds, want = delta
             infos = safetensors_io.get_compressed_tensors_metadata(meta)
@@ -229,6 +237,7 @@ class ResidentCheckpoint:
                 bad = [name for name in kinds if got[name] != want[name]]
                 if bad:
                     raise codec.DigestMismatch(bad, f"{path}: the base does not hold what the delta was taken over")
+        patched = cls._file_patches(path, {n: over[n] for n, k in kinds.items() if k == "sparse"}, check_patches)      # {name: (offset in the data section, L, T, elem)}
         up = safetensors_io._upload_file(path, dev, delta=delta is not None)
         if up is None:
             raise ValueError(f"{path}: the container names a dtype this loader does not know")
@@ -267,6 +276,22 @@ class ResidentCheckpoint:
                 e.delta, e.base = "same", ref
                 entries.append(e)
                 continue
+            if kinds.get(name) == "sparse":                        # the patch where the upload put it; the frame parameters the tensor would be coded with
+                tdt, tshape, ref = over[name]
+                at, L, T, elem = patched[name]
+                if ref[0] == "tensor":
+                    params = tuple(ZipNN(input_format="torch", bytearray_dtype=tdt, method=COMPRESSION_METHOD).torch_frame_plan(torch.empty(tshape, dtype=tdt, device="meta"))[1:])
+                else:
+                    params = (ref[2].P, ref[2].bits, ref[2].byts, ref[2].chunk)
+                if params[0] != elem:
+                    raise ValueError(f"{path}: {name!r}: {tdt} is not a dtype a patch describes")
+                e = _Entry(name, tdt, tshape, _numel(tshape) * elem, params=params)
+                e.patch, e.delta, e.base, e.entries = blob[at:at + L], "sparse", ref, T
+                if e.patch.data_ptr() % 16:                        # (the upload's allocation is aligned far beyond 16 bytes; should one not be, the apply kernel still needs it)
+                    e.patch = e.patch.clone()
+                    extra += L
+                entries.append(e)
+                continue
             if hi > lo:
                 es = torch.empty(0, dtype=dt).element_size()
                 raw = blob[lo:hi]
@@ -285,6 +310,12 @@ class ResidentCheckpoint:
                     e.restore = ref
         store = cls(dev, entries, blob.numel() + extra, keep=(blob,) + ((base,) if base is not None else ()))
         store._metadata = {k: v for k, v in up.metadata.items() if k not in (safetensors_io.METADATA_KEY, safetensors_io.DIGESTS_KEY, safetensors_io.DELTA_KEY)}
+        if patched and check_patches:                              # before anything is decoded: every patch whole, one launch, one read-back
+            sp = [e for e in entries if e.patch is not None]
+            verdicts, _ = codec.patch_check_device_batch(_capi.lib(), [(e.patch, e.nbytes, e.P) for e in sp], _stream_of(dev))
+            bad = [(e.name, v) for e, v in zip(sp, verdicts) if v]
+            if bad:
+                raise ValueError(f"{path}: malformed patch (znp1) in " + ", ".join(f"{n!r}: {codec.patch_verdict_text(v)}" for n, v in bad))
         if index:
             store.build_index(deltas=(index == "deltas"))
         if recorded is not None:
@@ -297,6 +328,43 @@ class ResidentCheckpoint:
         elif digests:
             store._digests = store._decoded_digests(store.keys())
         return store
+
+    @staticmethod
+    def _file_patches(path, over, check_slack):
+        """The "sparse" entries of a delta file, from the file alone, before anything is uploaded.  over: {name: (dtype, shape, _)} -> {name: (offset of the patch
+        in the data section, L, T, elem)}.  The patch starts at the entry's first multiple of 16; its header must describe the tensor and give the
+        entry's length; check_slack: the up to 15 bytes of the entry around the patch must be zero.  A ValueError names the tensor."""
+        if not over:
+            return {}
+        from . import safetensors_io
+        lay = safetensors_io._read_layout(path)
+        if lay is None:
+            raise ValueError(f"{path}: the container names a dtype this loader does not know")
+        _, layout, data_start = lay
+        lib, out = _capi.lib(), {}
+        with open(path, "rb") as f:
+            for name, (dt, shape, _) in over.items():
+                fdt, _, lo, hi = layout[name]
+                elem = torch.empty(0, dtype=dt).element_size()
+                n = _numel(shape) * elem
+                at = (lo + 15) // 16 * 16
+                if fdt != torch.uint8 or hi - lo < 32 + safetensors_io.SPARSE_SLACK:
+                    raise ValueError(f"{path}: {name!r} is listed as \"sparse\" but its entry of {hi - lo} bytes cannot hold a patch")
+                f.seek(data_start + lo)
+                head = f.read(at - lo + 32)
+                magic, E, T, L = head[at - lo: at - lo + 4], head[at - lo + 4], int.from_bytes(head[at - lo + 16: at - lo + 24], "little"), int.from_bytes(head[at - lo + 24: at - lo + 32], "little")
+                if magic != b"ZNP1" or E != elem or int.from_bytes(head[at - lo + 8: at - lo + 16], "little") != n:
+                    raise ValueError(f"{path}: {name!r}: the patch's header does not describe a {dt} tensor of {n} bytes")
+                if hi - lo != L + safetensors_io.SPARSE_SLACK:
+                    raise ValueError(f"{path}: {name!r}: an entry of {hi - lo} bytes for a patch of {L} (the entry is the patch and {safetensors_io.SPARSE_SLACK} bytes)")
+                if T > n // elem or lib.patch_len(n, elem, T) != L:
+                    raise ValueError(f"{path}: {name!r}: {L} bytes is not the length of a patch of {T} elements")
+                if check_slack:
+                    f.seek(data_start + at + L)
+                    if any(head[:at - lo]) or any(f.read(hi - at - L)):
+                        raise ValueError(f"{path}: {name!r}: the bytes around the patch are not zero")
+                out[name] = (at, L, T, elem)
+        return out
 
     @staticmethod
     def _ref_digests(refs, dev):
@@ -362,7 +430,7 @@ class ResidentCheckpoint:
         sparse=True (with base): a delta candidate is also COUNTED against its base — one pass, no bytes written — and where the "znp1" patch (the changed
         elements with their XOR values, include/zipnn_hip.h) would be smaller than the best body so far it is built and kept instead:
         info(name)["delta"] == "sparse".  The smallest of plain body, delta body and patch wins, ties in that order, so nothing that is chosen without
-        `sparse` changes.  Every read path serves such an entry (the base's bytes, then the patch applied in place); save_file does not yet.
+        `sparse` changes.  Every read path serves such an entry (the base's bytes, then the patch applied in place); save_file(sparse=True) writes it down.
         Peak memory of the build, beside `sd` on the device: the plain pass's compress arena (as large as the tensors, as without `base`); then the
         plain bodies and, as they come, the delta bodies — each a trimmed copy out of its arena —, plus per group of at most 1 GiB of tensors (or one
         larger tensor) the decoded tensors of a resident base and one arena of the group's size; at the end the kept bodies are copied once more into
@@ -694,7 +762,7 @@ class ResidentCheckpoint:
         h[24:32] = (HEADER_LEN + len(ext) + e.body.numel()).to_bytes(8, "little")      # (the total length, as the core writes it)
         return bytes(h) + ext
 
-    def save_file(self, path, digests=None, metadata=None):
+    def save_file(self, path, digests=None, metadata=None, sparse=False):
         """Write the store as a `.znn.safetensors` file -> path.  Any store: plain, indexed, a variant, a variant of a variant.  The bodies go out as they lie in
         device memory — one transfer to the host per allocation that holds them (one for a store from from_state_dict or from_file), never recompressed —,
         each behind the frame header that describes its parameters; a tensor whose header + body would not be smaller than the tensor is written as it is
@@ -706,39 +774,52 @@ class ResidentCheckpoint:
         from_file(path, device, base=...) / safetensors_io.load_file(path, device, base=...).
         digests: None writes `znn_digests` when the store has digests; True computes them (one decode of every tensor) where it has none; False omits them.
         metadata: the file's other metadata (default: what from_file found in the store's own file, else {"format": "pt"}).  The sync index is not saved:
-        from_file(index=True) rebuilds it.  A store with SPARSE entries is refused (ValueError naming them): patches have no file form yet."""
+        from_file(index=True) rebuilds it.
+        sparse: a store with SPARSE entries is refused (ValueError naming them, before `path` is touched) unless sparse=True, which writes them:
+        "sparse" under `znn_delta`, whose version is then 2 — earlier builds of this library refuse such a file by that number.  The entry is L + 15 bytes: the
+        patch as it lies in device memory — it leaves in the same trip as the bodies — at the entry's first offset in the data section that is a multiple of 16,
+        zero bytes around it, so that a loaded patch is a 16-byte aligned view of the uploaded data section.  safetensors decides where an entry lies: the file
+        is written with zero-filled entries under a temporary name, the patches are put at their places, and the file is renamed to `path`.  A patch whose
+        L + 15 bytes would not be smaller than the tensor is written as the tensor (one decode).  A store without sparse entries writes the same file either way."""
+        import os
         from safetensors.torch import save_file as st_save_file
         from . import safetensors_io
         lib = _capi.lib()
-        sparse = [e.name for e in self._entries.values() if e.patch is not None]
-        if sparse:
-            raise ValueError(f"save_file: the file format has no form for sparse entries yet (DESIGN §3.10): {', '.join(repr(n) for n in sparse[:8])}{' …' if len(sparse) > 8 else ''}"
-                             " — build the store without sparse=True to write it down")
+        patched = [e.name for e in self._entries.values() if e.patch is not None]
+        if patched and not sparse:
+            raise ValueError(f"save_file: the store holds sparse entries (DESIGN §3.10): {', '.join(repr(n) for n in patched[:8])}{' …' if len(patched) > 8 else ''}"
+                             " — pass sparse=True to write them as patches (DESIGN §3.11), or build the store without sparse=True")
         recorded = None
         if digests or (digests is None and self._digests is not None):
             recorded = self._digests if self._digests is not None else self._decoded_digests(self.keys())
-        # which bodies go out as frames, and the one trip of each allocation that holds them
+        # which bodies go out as frames and which patches as they are, and the one trip of each allocation that holds them
         framed, roots = {}, {}
         for e in self._entries.values():
-            if e.compressed:
-                hdr = self._frame_header(e)
-                if len(hdr) + e.body.numel() < e.nbytes:
-                    root = e.body._base if e.body._base is not None else e.body
-                    off = e.body.storage_offset() - root.storage_offset()
-                    key = (root.data_ptr(), root.numel())
-                    span = roots.setdefault(key, [root, off, off + e.body.numel()])
-                    span[1], span[2] = min(span[1], off), max(span[2], off + e.body.numel())
-                    framed[e.name] = (hdr, key, off)
+            hdr, held = (self._frame_header(e), e.body) if e.compressed else (b"", e.patch)
+            if held is not None and len(hdr) + held.numel() + (safetensors_io.SPARSE_SLACK if e.patch is not None else 0) < e.nbytes:
+                root = held._base if held._base is not None else held
+                off = held.storage_offset() - root.storage_offset()
+                key = (root.data_ptr(), root.numel())
+                span = roots.setdefault(key, [root, off, off + held.numel()])
+                span[1], span[2] = min(span[1], off), max(span[2], off + held.numel())
+                framed[e.name] = (hdr, key, off)
         host = {}
         with _device_of(self.device):
             for key, (root, lo, hi) in roots.items():
                 host[key] = (memoryview(codec.to_host(lib, root.reshape(-1)[lo:hi])), lo)
-        tensors, infos, kinds, refs = {}, {}, {}, {}
+        tensors, infos, kinds, refs, patches = {}, {}, {}, {}, {}
         order = sorted(self._entries)                              # (the order safetensors walks a file's names in: the metadata lists keep it, as compress_safetensors_file's do)
         for name in order:
             e = self._entries[name]
             like = torch.empty(e.shape, dtype=e.dtype, device="meta")
-            if name in framed:
+            if name in framed and e.patch is not None:             # a placeholder: the patch goes in once safetensors has said where the entry lies
+                hdr, key, off = framed[name]
+                mv, lo = host[key]
+                patches[name] = mv[off - lo: off - lo + e.patch.numel()]
+                tensors[name] = torch.zeros(e.patch.numel() + safetensors_io.SPARSE_SLACK, dtype=torch.uint8)
+                infos[name] = build_compressed_tensor_info(like)
+                kinds[name], refs[name] = "sparse", e.base
+            elif name in framed:
                 hdr, key, off = framed[name]
                 mv, lo = host[key]
                 frame = codec.new_bytearray(len(hdr) + e.body.numel())
@@ -762,7 +843,24 @@ class ResidentCheckpoint:
             safetensors_io._set_digests_metadata(metadata, order, [recorded[n] for n in order])
         if kinds:
             safetensors_io._set_delta_metadata(metadata, kinds, self._ref_digests(refs, self.device))
-        st_save_file(tensors, path, metadata)
+        if not patches:
+            st_save_file(tensors, path, metadata)
+            return path
+        tmp = f"{path}.tmp{os.getpid()}"
+        try:
+            st_save_file(tensors, tmp, metadata)
+            _, layout, data_start = safetensors_io._read_layout(tmp)
+            with open(tmp, "r+b") as f:
+                for name, mv in patches.items():
+                    lo, hi = layout[name][2], layout[name][3]
+                    at = (lo + 15) // 16 * 16                      # (of the DATA SECTION: what a reader uploads to an aligned allocation)
+                    assert hi - lo == len(mv) + safetensors_io.SPARSE_SLACK and at + len(mv) <= hi
+                    f.seek(data_start + at)
+                    f.write(mv)
+            os.replace(tmp, path)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
         return path
 
     # ---- decoding -------------------------------------------------------------------------------------------------------------

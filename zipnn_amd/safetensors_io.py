@@ -15,9 +15,13 @@ from .zipnn import (COMPRESSED_DTYPE, COMPRESSION_METHOD, METADATA_KEY, ZipNN, b
 SUFFIX = ".znn.safetensors"
 _DIGEST_GROUP_BYTES = 256 << 20      # compress_safetensors_file(digests=True), per-tensor path: tensors are digested as they are read, in groups of at most this many bytes
 DIGESTS_KEY = "znn_digests"          # file metadata: a JSON string {"algo": "zn64-1", "tensors": {name: 16 hex digits}} — digests of the DECODED bytes of every tensor
-DELTA_KEY = "znn_delta"              # file metadata of a DELTA file: a JSON string {"version": 1, "algo": "zn64-1", "tensors": {name: "delta" | "same"},
-                                     # "base_digests": {name: 16 hex digits}} — which tensors are coded over a base, and the digests of that base's tensors
+DELTA_KEY = "znn_delta"              # file metadata of a DELTA file: a JSON string {"version": 1 | 2, "algo": "zn64-1",
+                                     # "tensors": {name: "delta" | "same" | "sparse"}, "base_digests": {name: 16 hex digits}} — which tensors are coded over a base and
+                                     # how, and the digests of that base's tensors.  Version 2 is written exactly when a tensor is "sparse" (a "znp1" patch in an entry
+                                     # of L + 15 bytes, SPARSE_SLACK); a file without one is version 1, byte for byte what it was before there were patches in files.
 DELTA_VERSION = 1
+DELTA_VERSION_SPARSE = 2
+SPARSE_SLACK = 15                    # a "sparse" entry is the patch plus this many zero bytes: the patch starts at the entry's first 16-byte boundary of the data section
 
 
 def read_metadata(filename):
@@ -42,22 +46,23 @@ def file_digests(metadata):
 
 
 def file_delta(metadata):
-    """-> ({name: "delta" | "same"}, {name: digest of the BASE tensor's bytes}) from a delta file's metadata, or None for a file that is no delta file.
-    A version or a digest algorithm this library does not know, or an entry without its base digest, is an error."""
+    """-> ({name: "delta" | "same" | "sparse"}, {name: digest of the BASE tensor's bytes}) from a delta file's metadata, or None for a file that is no delta file.
+    A version or a digest algorithm this library does not know, a "sparse" entry in a version 1 file, or an entry without its base digest, is an error."""
     import json
     from . import codec
     raw = metadata.get(DELTA_KEY)
     if raw is None:
         return None
     d = json.loads(raw)
-    if d.get("version") != DELTA_VERSION:
-        raise ValueError(f"{DELTA_KEY}: unknown version {d.get('version')!r} (this library knows {DELTA_VERSION})")
+    if d.get("version") not in (DELTA_VERSION, DELTA_VERSION_SPARSE):
+        raise ValueError(f"{DELTA_KEY}: unknown version {d.get('version')!r} (this library knows {DELTA_VERSION} and {DELTA_VERSION_SPARSE})")
     if d.get("algo") != codec.DIGEST_ALGO:
         raise ValueError(f"{DELTA_KEY}: unknown digest algorithm {d.get('algo')!r} (this library knows {codec.DIGEST_ALGO!r})")
     kinds = dict(d.get("tensors") or {})
-    odd = [n for n, k in kinds.items() if k not in ("delta", "same")]
+    known = ("delta", "same") if d.get("version") == DELTA_VERSION else ("delta", "same", "sparse")
+    odd = [n for n, k in kinds.items() if k not in known]
     if odd:
-        raise ValueError(f"{DELTA_KEY}: {odd[0]!r} is neither \"delta\" nor \"same\"")
+        raise ValueError(f"{DELTA_KEY}: {odd[0]!r} is {kinds[odd[0]]!r}: a version {d.get('version')} file knows " + ", ".join(f'"{k}"' for k in known))
     base = {name: int(h, 16) for name, h in (d.get("base_digests") or {}).items()}
     missing = [n for n in kinds if n not in base]
     if missing:
@@ -68,7 +73,8 @@ def file_delta(metadata):
 def _set_delta_metadata(metadata, kinds, base_digests):
     import json
     from . import codec
-    metadata[DELTA_KEY] = json.dumps({"version": DELTA_VERSION, "algo": codec.DIGEST_ALGO, "tensors": dict(kinds),
+    version = DELTA_VERSION_SPARSE if "sparse" in kinds.values() else DELTA_VERSION
+    metadata[DELTA_KEY] = json.dumps({"version": version, "algo": codec.DIGEST_ALGO, "tensors": dict(kinds),
                                       "base_digests": {n: f"{base_digests[n]:016x}" for n in kinds}})
 
 
@@ -95,7 +101,7 @@ def check_digests(tensors, want, what):
         raise codec.DigestMismatch(bad, f"{what}: decoded bytes differ from the file's digests")
 
 
-def compress_safetensors_file(filename, out_path=None, device="cpu", method=None, batched=None, digests=False, base=None):
+def compress_safetensors_file(filename, out_path=None, device="cpu", method=None, batched=None, digests=False, base=None, sparse=False):
     """-> path of the compressed file.  `device` = where tensors are staged for compression
     ("cuda:N" compresses in HBM; the compressed frames come back to the host for writing).  Tensors staged in HBM
     are compressed by ONE batched call for the whole file (`batched=None`: automatic; True forces it).
@@ -105,13 +111,15 @@ def compress_safetensors_file(filename, out_path=None, device="cpu", method=None
     it.  Readers that do not know the key ignore it; with the default the file is byte for byte what it was without this option.
     base: write a DELTA file over it — a path to the base's `.safetensors` or `.znn.safetensors`, a ResidentCheckpoint on the device, or a mapping
     of names to device tensors: the file's tensors go to the device, become a variant store over the base (ResidentCheckpoint.from_state_dict(base=)) and that
-    store is saved (ResidentCheckpoint.save_file).  A device is needed for it: with device="cpu" the current GPU is used."""
+    store is saved (ResidentCheckpoint.save_file).  A device is needed for it: with device="cpu" the current GPU is used.
+    sparse=True (with base): tensors with few changed elements become "znp1" patches (from_state_dict(sparse=True)) and are written as such (save_file(sparse=True),
+    DESIGN §3.11)."""
     from safetensors import safe_open
     from safetensors.torch import save_file
     assert filename.endswith(".safetensors")
     out_path = out_path or filename[: -len(".safetensors")] + SUFFIX
     if base is not None:
-        return _compress_file_over_base(filename, out_path, device, method, digests, base)
+        return _compress_file_over_base(filename, out_path, device, method, digests, base, sparse)
     if torch.device(device).type == "cuda" and batched is not False:
         done = _compress_file_on_device(filename, out_path, torch.device(device), method, digests)
         if done is not None:
@@ -181,7 +189,7 @@ def _base_store(base, dev):
     return base
 
 
-def _compress_file_over_base(filename, out_path, device, method, digests, base):
+def _compress_file_over_base(filename, out_path, device, method, digests, base, sparse=False):
     """compress_safetensors_file(base=): file -> delta file, through the store path (no second writer)."""
     from . import codec
     from .resident import ResidentCheckpoint
@@ -190,17 +198,18 @@ def _compress_file_over_base(filename, out_path, device, method, digests, base):
         dev = torch.device("cuda", codec.current_device())
     dev = ResidentCheckpoint._work_device(dev)
     tensors = load_file(filename, dev)
-    store = ResidentCheckpoint.from_state_dict(tensors, dev, method=method, base=_base_store(base, dev), digests=bool(digests))
+    store = ResidentCheckpoint.from_state_dict(tensors, dev, method=method, base=_base_store(base, dev), digests=bool(digests), sparse=bool(sparse))
     del tensors
-    return store.save_file(out_path, digests=bool(digests), metadata=read_metadata(filename) or None)
+    return store.save_file(out_path, digests=bool(digests), metadata=read_metadata(filename) or None, sparse=bool(sparse))
 
 
-def save_file(tensors, filename, device="cuda:0", base=None, digests=False, metadata=None):
-    """safetensors.torch.save_file for live tensors, compressed: ResidentCheckpoint.from_state_dict(tensors, device, base=base, digests=digests) followed by its
-    save_file — with `base` (a store on the device, a mapping of device tensors, a module) a DELTA file over it.  -> filename."""
+def save_file(tensors, filename, device="cuda:0", base=None, digests=False, metadata=None, sparse=False):
+    """safetensors.torch.save_file for live tensors, compressed: ResidentCheckpoint.from_state_dict(tensors, device, base=base, digests=digests, sparse=sparse)
+    followed by its save_file — with `base` (a store on the device, a mapping of device tensors, a module) a DELTA file over it, with sparse=True
+    one whose tensors with few changed elements are patches.  -> filename."""
     from .resident import ResidentCheckpoint
-    store = ResidentCheckpoint.from_state_dict(tensors, device, base=base, digests=bool(digests))
-    return store.save_file(filename, digests=bool(digests), metadata=metadata)
+    store = ResidentCheckpoint.from_state_dict(tensors, device, base=base, digests=bool(digests), sparse=bool(sparse))
+    return store.save_file(filename, digests=bool(digests), metadata=metadata, sparse=bool(sparse))
 
 
 def _compress_file_on_device(filename, out_path, dev, method, digests=False):
@@ -381,7 +390,7 @@ class _Uploaded:
 def _upload_file(filename, device, delta=False):
     """First half of decode_file_on_device, and how resident.ResidentCheckpoint.from_file gets its frames into HBM: every frame header parsed
     from the host mapping, then the file's data section to the device in ONE transfer.  -> _Uploaded, or None when the container names a dtype
-    this parser does not know.  A delta file (znn_delta) is refused unless the caller says it brings the base (delta=True): its "same" entries hold no frame."""
+    this parser does not know.  A delta file (znn_delta) is refused unless the caller says it brings the base (delta=True): its "same" and "sparse" entries hold no frame."""
     import contextlib
     import mmap
     import threading
@@ -401,7 +410,7 @@ def _upload_file(filename, device, delta=False):
     kinds = file_delta(metadata)
     if kinds is not None and not delta:
         raise _needs_base(filename)
-    skip = frozenset(n for n, k in kinds[0].items() if k == "same") if kinds is not None else ()
+    skip = frozenset(n for n, k in kinds[0].items() if k in ("same", "sparse")) if kinds is not None else ()      # (no frame: nothing, or a patch)
     with open(filename, "rb") as f:
         size = os.fstat(f.fileno()).st_size
         mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if size else None
