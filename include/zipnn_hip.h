@@ -369,6 +369,31 @@ int zn_patch_check_batch_dev(const zn_patch_check_item* items, size_t count,
                              unsigned long long* entries_out,   /* host, may be NULL: T of each well-formed item */
                              void* stream);
 
+/* MERGING PATCHES.  Patches are XOR lists, so two patches of one tensor combine without the tensor: the XOR-merge a (+) b holds the union of their elements, the
+ * XOR of the two values where both have an entry, and no entry where that XOR is zero.  The format is canonical, so the result is unique, and it is byte for
+ * byte what zn_patch_build_batch_dev builds from the tensors the merge never sees: merging the patch of A over a base with the patch of B over the same base
+ * gives the patch of B over A (and of A over B — the merge is symmetric); merging the patches of consecutive steps s1 over s0, s2 over s1, … gives the patch of
+ * the last step over s0.
+ * zn_patch_merge_size_batch_dev: the count pass alone — sizes_out[i] = L of item i's merge, or 0 when everything cancels; one read-back; d_out / out_cap ignored.
+ * zn_patch_merge_batch_dev: count, scan (zn_k_patch_scan), one read-back, emit; synchronous.  out_len = L, or 0 (nothing written) when everything cancels — the
+ *   convention of an identical pair in build.  ZN_E_CAP when a capacity is short: every out_len then holds what is needed and nothing was written.
+ * Both inputs describe a tensor of n bytes in elements of `elem` (eligible as above).  d_a, d_b and d_out 16-byte aligned, a_len and b_len >= 32, and
+ * [d_out, d_out + out_cap) overlaps neither input; anything else — or an (n, elem) that is not eligible — is ZN_E_ARG before any launch.
+ * Inputs may come from anywhere.  The kernels read nothing outside [d_x, d_x + x_len) — the header first: magic, E and n against the item, L against x_len and
+ * the formula's value for T; then first[0] == 0, first[b] <= first[b + 1] <= T, first[NB] == T — and EVERY block of both inputs is visited, so a merge that
+ * returns ZN_OK has validated both inputs whole: no offset beyond the tensor's last element, offsets strictly ascending inside a block, no zero value.  Only the
+ * canonical padding is not looked at (zn_patch_check_batch_dev's ZN_PATCH_BAD_PADDING).  Anything wrong in any input of any item is ZN_E_CORRUPT for the call:
+ * the outputs are then unspecified, and nothing outside [d_out, d_out + out_cap) was written. */
+typedef struct zn_patch_merge_item {
+  const void* d_a; size_t a_len;            /* 16-byte aligned, len >= 32 */
+  const void* d_b; size_t b_len;
+  size_t n; int elem;                       /* the tensor both patches cover */
+  void* d_out; size_t out_cap;              /* 16-byte aligned; overlaps neither input */
+  size_t out_len;                           /* out */
+} zn_patch_merge_item;
+int zn_patch_merge_size_batch_dev(const zn_patch_merge_item* items, size_t count, size_t* sizes_out, void* stream);
+int zn_patch_merge_batch_dev(zn_patch_merge_item* items, size_t count, void* stream);
+
 /* Plumbing for callers that keep the tensors in HBM but hold pageable host buffers (files, Python bytes): the same
  * pinned, multi-threaded transfer the host-buffer entry points above use internally (zipnn_amd/csrc/zn_host_pipe.hpp),
  * on the current device; returns when the n bytes have arrived.  No reference counterpart — the reference's buffers

@@ -39,6 +39,10 @@ blocks of leg b as the base, the two fine-tunes of --delta:
 --sparse: sparse variant stores instead (from_state_dict(..., base=..., sparse=True)), into profiles/resident_sparse.{json,txt}:
   s  per fine-tune of --delta, over a resident indexed base: resident bytes and build time without and with sparse=True; plan.run of one block from either
      store, interleaved in both orders (A B A B B A B A: the four runs of the delta store are the A/A spread); apply_ + revert_ of one block from either
+--rebase: patch merges and ResidentCheckpoint.rebased instead, into profiles/resident_rebase.{json,txt}:
+  r  a chain of four 2 % steps and two sibling fine-tunes over a resident indexed base, every comparison interleaved in both orders (A B A B B A B A: the four A
+     runs are the A/A spread): rebased against get_tensors + from_state_dict; the merge call against the build call on the same pairs; plan.run of one block
+     from the chain against the flattened store; sw.apply_ against a.revert_ + b.apply_; resident bytes of b over the base against b over a
 """
 import argparse
 import json
@@ -734,6 +738,139 @@ def leg_s(args):
     return res
 
 
+def leg_r(args):
+    """--rebase: see the module docstring."""
+    import torch
+    from zipnn_amd import ResidentCheckpoint, _capi, codec
+    lib = _capi.lib()
+    sd, per = _blocks(args.layers)
+    names = per[0]
+    base = ResidentCheckpoint.from_state_dict(sd, "cuda:0", index=True)
+    sds, chain = [sd], [base]
+    for k in range(4):
+        sds.append(_fine_tune(sds[-1], "sparse", 41 + k))
+        chain.append(ResidentCheckpoint.from_state_dict(sds[-1], "cuda:0", base=chain[-1], sparse=True))
+    s4, ft4 = chain[-1], sds[-1]
+    order = ("A", "B", "A", "B", "B", "A", "B", "A")
+
+    def wall(fn):
+        torch.cuda.synchronize(); t0 = time.perf_counter(); r = fn(); torch.cuda.synchronize()
+        return r, (time.perf_counter() - t0) * 1e3
+
+    def abab(fa, fb, timer):
+        runs = {"A": [], "B": []}
+        for leg in order:
+            runs[leg].append(timer(fa if leg == "A" else fb))
+        a, b = runs["A"], runs["B"]
+        return {"A_ms": a, "B_ms": b, "aa_spread": (max(a) - min(a)) / min(a), "B_over_A": (sum(b) / len(b)) / (sum(a) / len(a))}
+    res = {"layers": args.layers, "tensors": len(sd), "nbytes": base.nbytes,
+           "sparse_entries_s4": sum(1 for k in ft4 if s4.info(k)["delta"] == "sparse"), "patch_entries_s4": sum(s4.info(k)["patch_entries"] or 0 for k in ft4)}
+    # 1. the chain flattened: rebased (B) against the route it replaces (A)
+    flat = s4.rebased(base)
+    for k in ft4:
+        assert flat.info(k)["delta"] == s4.info(k)["delta"] or flat.info(k)["delta"] == "sparse", k
+    got = flat.get_tensors(list(ft4))
+    for k in ft4:
+        assert _same(got[k], ft4[k]), ("flat", k)
+    del got
+    res["flat_sparse_entries"] = sum(1 for k in ft4 if flat.info(k)["delta"] == "sparse")
+    res["flat_patch_entries"] = sum(flat.info(k)["patch_entries"] or 0 for k in ft4)
+    res["flat_resident_bytes"], res["s4_resident_bytes"] = flat.resident_bytes, s4.resident_bytes
+    res["rebase_wall"] = abab(lambda: ResidentCheckpoint.from_state_dict(s4.get_tensors(list(ft4)), "cuda:0", base=base, sparse=True), lambda: s4.rebased(base),
+                              lambda fn: wall(fn)[1])
+    s4.rebased(base)
+    res["rebase_kernels"] = _capi_kernels()
+    # 2. the merge call alone (B) against the build call on the same pairs from materialised tensors (A): patch(s1 over base) (+) patch(s2 over s1) = patch(s2 over base)
+    sp = [k for k in sd if chain[1].info(k)["delta"] == "sparse" and chain[2].info(k)["delta"] == "sparse"]
+    pa, pb = [chain[1]._entries[k].patch for k in sp], [chain[2]._entries[k].patch for k in sp]
+    tri = [(a, b, sd[k].numel() * 2, 2) for a, b, k in zip(pa, pb, sp)]
+    sizes = codec.patch_merge_sizes_device_batch(lib, tri)
+    pairs = [(codec.flat_bytes(sds[2][k]), codec.flat_bytes(sd[k]), 2) for k in sp]
+    assert codec.patch_sizes_device_batch(lib, pairs) == sizes
+    offs, o = [], 0
+    for n in sizes:
+        offs.append(o); o += (n + 255) // 256 * 256
+    out_m, out_b = (torch.empty(max(o, 16), dtype=torch.uint8, device="cuda") for _ in range(2))
+    mi = [(a.data_ptr(), a.numel(), b.data_ptr(), b.numel(), n, el, out_m.data_ptr() + off, cap) for (a, b, n, el), off, cap in zip(tri, offs, sizes)]
+    bi = [(s.data_ptr(), b.data_ptr(), s.numel(), el, out_b.data_ptr() + off, cap) for (s, b, el), off, cap in zip(pairs, offs, sizes)]
+    st = torch.cuda.current_stream().cuda_stream
+    assert lib.patch_merge_batch_dev(mi, st) == sizes and lib.patch_build_batch_dev(bi, st) == sizes
+    for off, n in zip(offs, sizes):
+        assert torch.equal(out_m[off:off + n], out_b[off:off + n]), "the merge is not the build"
+    res["merge_call"] = abab(lambda: lib.patch_build_batch_dev(bi, st), lambda: lib.patch_merge_batch_dev(mi, st), lambda fn: _events_ms(fn, args.reps)["median_ms"])
+    res["merge_call"].update({"items": len(sp), "input_bytes": sum(a.numel() + b.numel() for a, b in zip(pa, pb)), "output_bytes": sum(sizes),
+                              "tensor_bytes": sum(sd[k].numel() * 2 for k in sp)})
+    del out_m, out_b
+    # 3. plan.run of one block: the depth-4 chain (A) against the flattened store (B)
+    scratch = torch.empty(flat.scratch_bytes(names), dtype=torch.uint8, device="cuda")
+
+    def plan_ms(store):
+        plan = store.plan(names, into=scratch)
+        t = _events_ms(plan.run, args.reps)["median_ms"]
+        plan.status()
+        for k in names:
+            assert _same(plan.tensors[k], ft4[k]), k
+        plan.close()
+        return t
+    res["plan_run"] = abab(lambda: s4, lambda: flat, lambda pick: plan_ms(pick()))
+    # 4. live weights from sibling a to sibling b and back: a.revert_ + b.apply_ + b.revert_ + a.apply_ (A) against sw.apply_ + sw.revert_ (B); 5. resident bytes
+    a, fa = chain[1], sds[1]
+    fb = _fine_tune(sd, "sparse", 77)
+    b = ResidentCheckpoint.from_state_dict(fb, "cuda:0", base=base, sparse=True)
+    sw = b.rebased(a)
+    live = {k: fa[k].clone() for k in names}
+    sw.apply_(live)
+    for k in names:
+        assert _same(live[k], fb[k]), ("sw.apply_", k)
+    sw.revert_(live)
+    for k in names:
+        assert _same(live[k], fa[k]), ("sw.revert_", k)
+    res["switch"] = abab(lambda: (a.revert_(live, check=False), b.apply_(live, check=False), b.revert_(live, check=False), a.apply_(live, check=False)),
+                         lambda: (sw.apply_(live, check=False), sw.revert_(live, check=False)), lambda fn: _events_ms(fn, args.reps)["median_ms"])
+    a.status()
+    for k in names:
+        assert _same(live[k], fa[k]), ("switch", k)
+    res["sibling_bytes"] = {"b_over_base": b.resident_bytes, "b_over_a": sw.resident_bytes, "a_over_base": a.resident_bytes, "nbytes": b.nbytes,
+                            "entries_b_over_base": sum(b.info(k)["patch_entries"] or 0 for k in fb), "entries_b_over_a": sum(sw.info(k)["patch_entries"] or 0 for k in fb)}
+    return res
+
+
+def main_rebase(args):
+    p = subprocess.run(["timeout", "-k", "10", "900", sys.executable, os.path.abspath(__file__), "--leg", "r", "--layers", str(args.layers), "--reps", str(args.reps)],
+                       capture_output=True, text=True)
+    line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+    if p.returncode != 0 or not line:
+        print(f"leg r failed (exit {p.returncode})\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}")
+        return p.returncode or 1
+    res = json.loads(line[0][7:])
+    out = args.out if args.out != os.path.join(ROOT, "profiles", "resident_decode") else os.path.join(ROOT, "profiles", "resident_rebase")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+
+    def row(title, r, a, b):
+        return [f"  {title}", f"          {a} " + " / ".join(f"{x:.4f}" for x in r["A_ms"]) + f"   {b} " + " / ".join(f"{x:.4f}" for x in r["B_ms"]) +
+                f"   ms; {b} = {r['B_over_A']:.3f} of {a}  (A/A spread of the {a} runs: {100 * r['aa_spread']:.1f} %)"]
+    m, sb = res["merge_call"], res["sibling_bytes"]
+    lines = [f"command: python scripts/bench_resident.py --rebase --layers {args.layers} --reps {args.reps}",
+             "patch merge probe (zn_patch_merge_batch_dev, ResidentCheckpoint.rebased, DESIGN §3.12): a chain of four steps, each 2 % of the elements replaced, and two sibling",
+             f"fine-tunes over a resident indexed base of {res['layers']} Llama-3-8B blocks (bf16, {res['tensors']} tensors, {res['nbytes']} B); every comparison interleaved in both orders",
+             "(A B A B B A B A), every result checked against the tensors",
+             f"  s4 over s3: {res['sparse_entries_s4']} sparse tensors, {res['patch_entries_s4']} entries, the chain's last store holds {res['s4_resident_bytes']} B;"
+             f" flattened over the base: {res['flat_sparse_entries']} sparse tensors, {res['flat_patch_entries']} entries, {res['flat_resident_bytes']} B"]
+    lines += row("1. the chain flattened, wall ms: get_tensors(s4) + from_state_dict(base=base, sparse=True) against s4.rebased(base)", res["rebase_wall"], "build", "rebased")
+    lines.append(f"          kernels of rebased's last call [{res['rebase_kernels']}]")
+    lines += row(f"2. the call alone, device events, median ms: zn_patch_build_batch_dev from the tensors ({m['tensor_bytes']} B twice) against zn_patch_merge_batch_dev on the two patches"
+                 f" of the same {m['items']} pairs ({m['input_bytes']} B in, {m['output_bytes']} B out)", m, "build", "merge")
+    lines += row("3. plan.run of one block, device events, median ms: from the depth-4 chain against the flattened store", res["plan_run"], "chain", "flat")
+    lines += row("4. live weights of one block from a to b and back, device events, median ms: a.revert_ + b.apply_ + b.revert_ + a.apply_ against sw.apply_ + sw.revert_ (sw = b.rebased(a))",
+                 res["switch"], "two-stores", "sw")
+    lines.append(f"  5. resident bytes: b over the base {sb['b_over_base']} B ({sb['entries_b_over_base']} entries), b over a {sb['b_over_a']} B ({sb['entries_b_over_a']} entries),"
+                 f" a over the base {sb['a_over_base']} B; the tensors {sb['nbytes']} B")
+    open(out + ".txt", "w").write("\n".join(lines) + "\n")
+    json.dump(res, open(out + ".json", "w"), indent=1)
+    print("\n".join(lines))
+    return 0
+
+
 def main_sparse(args):
     p = subprocess.run(["timeout", "-k", "10", "540", sys.executable, os.path.abspath(__file__), "--leg", "s", "--layers", str(args.layers), "--reps", str(args.reps)],
                        capture_output=True, text=True)
@@ -900,6 +1037,7 @@ def main():
     ap.add_argument("--delta-index", action="store_true", help="the DELTA sync index leg (p) instead of a-e")
     ap.add_argument("--sparse", action="store_true", help="the sparse variant leg (s) instead of a-e")
     ap.add_argument("--sparse-file", action="store_true", help="the sparse file leg (f) instead of a-e")
+    ap.add_argument("--rebase", action="store_true", help="the patch merge / rebased leg (r) instead of a-e")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resident_decode"))
     args = ap.parse_args()
     if args.leg:                                          # a child: one leg, its result as one JSON line
@@ -919,6 +1057,8 @@ def main():
         return main_sparse(args)
     if args.sparse_file:
         return main_sparse_file(args)
+    if args.rebase:
+        return main_rebase(args)
     results = {}
     for leg, limit in LEG_SECONDS.items():
         p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--layers", str(args.layers), "--reps", str(args.reps)],

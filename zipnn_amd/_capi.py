@@ -106,6 +106,15 @@ class ZnPatchCheckItem(ctypes.Structure):
     _fields_ = [("d_patch", ctypes.c_void_p), ("patch_len", ctypes.c_size_t), ("n", ctypes.c_size_t), ("elem", ctypes.c_int)]
 
 
+class ZnPatchMergeItem(ctypes.Structure):
+    """struct zn_patch_merge_item of include/zipnn_hip.h"""
+    _fields_ = [("d_a", ctypes.c_void_p), ("a_len", ctypes.c_size_t), ("d_b", ctypes.c_void_p), ("b_len", ctypes.c_size_t),
+                ("n", ctypes.c_size_t), ("elem", ctypes.c_int), ("d_out", ctypes.c_void_p), ("out_cap", ctypes.c_size_t), ("out_len", ctypes.c_size_t)]
+
+
+assert ctypes.sizeof(ZnPatchMergeItem) == 72
+
+
 # the bits of a zn_patch_check_batch_dev verdict
 PATCH_BAD_HEADER, PATCH_BAD_FIRST, PATCH_BAD_OFFSET, PATCH_BAD_VALUE, PATCH_BAD_PADDING = 1, 2, 4, 8, 16
 
@@ -225,6 +234,11 @@ class ZnLib:
             L.zn_patch_check_batch_dev.restype = ci
             L.zn_patch_check_batch_dev.argtypes = [ctypes.POINTER(ZnPatchCheckItem), sz, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_ulonglong), vp]
         L.zn_copy_to_device.restype = ci; L.zn_copy_to_device.argtypes = [vp, vp, sz]
+        if hasattr(L, "zn_patch_merge_batch_dev"):      # (likewise: a library from before the merge)
+            L.zn_patch_merge_size_batch_dev.restype = ci
+            L.zn_patch_merge_size_batch_dev.argtypes = [ctypes.POINTER(ZnPatchMergeItem), sz, ctypes.POINTER(sz), vp]
+            L.zn_patch_merge_batch_dev.restype = ci
+            L.zn_patch_merge_batch_dev.argtypes = [ctypes.POINTER(ZnPatchMergeItem), sz, vp]
         L.zn_copy_to_host.restype = ci; L.zn_copy_to_host.argtypes = [vp, vp, sz]
         L.zn_release_workspace.restype = ci
         L.zn_set_legacy_tree_descriptions.restype = ci
@@ -664,6 +678,32 @@ class ZnLib:
         entries = (ctypes.c_ulonglong * max(len(items), 1))()
         self._check(self._L.zn_patch_check_batch_dev(arr, len(items), verdicts, entries, ctypes.c_void_p(stream or None)))
         return [int(verdicts[i]) for i in range(len(items))], [int(entries[i]) for i in range(len(items))]
+
+    @staticmethod
+    def _patch_merge_items(items):
+        items = list(items)
+        arr = (ZnPatchMergeItem * max(len(items), 1))()
+        for i, it in enumerate(items):
+            ap, al, bp, bl, n, el = it[:6]
+            arr[i].d_a = ap or None; arr[i].a_len = al; arr[i].d_b = bp or None; arr[i].b_len = bl; arr[i].n = n; arr[i].elem = el
+            if len(it) > 6:
+                arr[i].d_out = it[6] or None; arr[i].out_cap = it[7]
+        return arr, len(items)
+
+    def patch_merge_size_batch_dev(self, items, stream=0):
+        """zn_patch_merge_size_batch_dev.  items: iterable of (a_ptr, a_len, b_ptr, b_len, n, elem) -> the merged patches' lengths (0: everything cancels);
+        the count pass only.  A malformed input is ZnError(ZN_E_CORRUPT)."""
+        arr, n = self._patch_merge_items(items)
+        out = (ctypes.c_size_t * max(n, 1))()
+        self._check(self._L.zn_patch_merge_size_batch_dev(arr, n, out, ctypes.c_void_p(stream or None)))
+        return [int(out[i]) for i in range(n)]
+
+    def patch_merge_batch_dev(self, items, stream=0):
+        """zn_patch_merge_batch_dev.  items: iterable of (a_ptr, a_len, b_ptr, b_len, n, elem, out_ptr, out_cap) -> the merged patches' lengths (0: everything
+        cancels, nothing written)."""
+        arr, n = self._patch_merge_items(items)
+        self._check(self._L.zn_patch_merge_batch_dev(arr, n, ctypes.c_void_p(stream or None)))
+        return [int(arr[i].out_len) for i in range(n)]
 
     def decode_status(self, stream=0):
         """zn_decode_status: wait for `stream`, raise what the last check=False decode call on this device would have raised."""

@@ -319,6 +319,75 @@ def patch_apply_(t, patch, check=True):
     return t
 
 
+def _patch_merge_items(triples):
+    triples = list(triples)
+    for a, b, _, _ in triples:
+        if (a.dtype != torch.uint8 or b.dtype != torch.uint8 or a.device != triples[0][0].device or b.device != a.device
+                or not a.is_contiguous() or not b.is_contiguous()):
+            raise ValueError("patch merge: contiguous uint8 tensors on one device")
+    return triples
+
+
+def patch_merge_sizes_device_batch(lib, triples):
+    """triples: [(patch a, patch b, n: the tensor's bytes, elem)] on one device, the patches contiguous uint8 tensors at 16-byte aligned addresses -> the
+    lengths of their XOR-merges (0: everything cancels): the count pass alone, one read-back.  It validates both inputs whole (ZnError(ZN_E_CORRUPT))."""
+    triples = _patch_merge_items(triples)
+    if not triples:
+        return []
+    dev = triples[0][0].device
+    with torch.cuda.device(dev) if dev.type == "cuda" else _nullctx():
+        return lib.patch_merge_size_batch_dev([(a.data_ptr(), a.numel(), b.data_ptr(), b.numel(), n, el) for a, b, n, el in triples], _stream_handle(triples[0][0]))
+
+
+def patch_merge_device_batch(lib, triples, sizes=None, return_arena=False):
+    """triples as for patch_merge_sizes_device_batch -> the merged patches: uint8 tensors (views of one allocation, each at a multiple of 256 bytes), None where
+    everything cancels — by ONE zn_patch_merge_batch_dev call.  sizes: the lengths patch_merge_sizes_device_batch gave for the same triples (else they are
+    counted here).  return_arena: (arena, offsets, lengths) instead."""
+    triples = _patch_merge_items(triples)
+    if not triples:
+        return (None, [], []) if return_arena else []
+    if sizes is None:
+        sizes = patch_merge_sizes_device_batch(lib, triples)
+    dev = triples[0][0].device
+    offs, o = [], 0
+    for n in sizes:
+        offs.append(o)
+        o += (n + 255) // 256 * 256
+    arena = torch.empty(max(o, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev) if dev.type == "cuda" else _nullctx():
+        lens = lib.patch_merge_batch_dev([(a.data_ptr(), a.numel(), b.data_ptr(), b.numel(), n, el, arena.data_ptr() + off if cap else 0, cap)
+                                          for (a, b, n, el), off, cap in zip(triples, offs, sizes)], _stream_handle(arena))
+    if return_arena:
+        return arena, offs, lens
+    return [arena[off:off + n] if n else None for off, n in zip(offs, lens)]
+
+
+def _patch_header(p, what):
+    import struct
+    if p.dtype != torch.uint8 or not p.is_contiguous() or p.numel() < 32:
+        raise ValueError(f"patch_merge: {what} is a contiguous uint8 tensor of at least 32 bytes")
+    h = bytes(p[:32].cpu().numpy())
+    if h[:4] != b"ZNP1":
+        raise ValueError(f"patch_merge: {what} is not a znp1 patch")
+    return h[4], struct.unpack_from("<Q", h, 8)[0]
+
+
+def patch_merge(pa, pb):
+    """The XOR-merge of two "znp1" patches of one tensor (include/zipnn_hip.h): the union of their elements, the XOR of the values where both have an entry, no
+    entry where that is zero.  With pa = patch_build(A, base) and pb = patch_build(B, base) the result is patch_build(B, A), byte for byte, without A, B or the
+    base: patch_apply_ of it turns a tensor that holds A into B, and back.  pa, pb: uint8 tensors on one device; the tensor's size and element size are read
+    from their headers, which must agree (ValueError).  -> the merged patch, or None when they cancel.  Both inputs are validated whole on the way: a malformed
+    one raises ZnError(ZN_E_CORRUPT)."""
+    from . import _capi
+    if pa.device != pb.device:
+        raise ValueError("patch_merge: two patches on one device")
+    (ea, na), (eb, nb) = _patch_header(pa, "the first patch"), _patch_header(pb, "the second patch")
+    if (ea, na) != (eb, nb):
+        raise ValueError(f"patch_merge: the patches describe different tensors ({na} bytes in elements of {ea} against {nb} in elements of {eb})")
+    pa, pb = (p if p.data_ptr() % 16 == 0 else p.clone() for p in (pa, pb))
+    return patch_merge_device_batch(_capi.lib(), [(pa, pb, na, ea)])[0]
+
+
 PATCH_BAD_NAMES = ((1, "header"), (2, "first"), (4, "offset"), (8, "value"), (16, "padding"))      # the ZN_PATCH_BAD_* bits of a check verdict
 
 

@@ -166,6 +166,13 @@ void zn_launch_patch_apply(const ZnPatchASeg& one, const ZnPatchASeg* d_segs, ui
 // elements — and its slot of the launch's verdict words: d_words[2 slot] collects the ZN_PATCH_BAD_* bits, d_words[2 slot + 1] receives the header's T.
 struct ZnPatchCSeg { const uint8_t* patch; uint64_t patch_len; uint64_t n; uint32_t wg0; uint32_t E; uint32_t slot; uint32_t pad_; };
 void zn_launch_patch_check(const ZnPatchCSeg& one, const ZnPatchCSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_words, hipStream_t stream);
+// ---- the XOR-merge of two patches : zn_patch_merge.hip ----
+// One item of a merge launch: the two patches of one tensor of m elements of E bytes, where the emit pass writes (16-byte aligned); its first workgroup — one per
+// block, one for a tensor without elements — and where its NB + 1 words start in the launch's scratch words (as ZnPatchBSeg's: the scan between the passes is
+// zn_k_patch_scan, over a ZnPatchBSeg table with the same m and w0).  d_status: one word, ZN_DEV_CORRUPT when an input is malformed.
+struct ZnPatchMSeg { const uint8_t* a; uint64_t a_len; const uint8_t* b; uint64_t b_len; uint8_t* out; uint64_t m; uint32_t wg0; uint32_t w0; uint32_t E; uint32_t pad_; };
+void zn_launch_patch_merge_count(const ZnPatchMSeg& one, const ZnPatchMSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_words, uint32_t* d_status, hipStream_t stream);
+void zn_launch_patch_merge_emit(const ZnPatchMSeg& one, const ZnPatchMSeg* d_segs, uint32_t nseg, uint32_t total_wg, const uint32_t* d_words, uint32_t* d_status, hipStream_t stream);
 
 // kernel-name log for zn_last_kernels()
 void zn_note_kernel(const char* name);

@@ -145,6 +145,7 @@ class ResidentCheckpoint:
         ft.info(n)["delta"]       # True, False or "same"
         ft = ResidentCheckpoint.from_state_dict(ft_sd, "cuda:0", base=base, sparse=True)      # tensors with few changed elements are kept as "znp1" patches
         ft.info(n)["delta"], ft.info(n)["patch_entries"]                                          # "sparse", the number of elements that differ
+        flat = s3.rebased(base); sw = ft_b.rebased(ft_a)      # the same tensors over another store: a chain flattened, a sibling re-parented — by patch merges
 
     CONTENT DIGESTS ("zn64-1"; an error-detecting code, not a cryptographic hash) let a store answer whether what it decodes is still what it was built from:
 
@@ -570,6 +571,134 @@ class ResidentCheckpoint:
         store._digests = recorded
         if index:
             store.build_index(deltas=(index == "deltas"))
+        return store
+
+    # ---- re-parenting a variant ------------------------------------------------------------------------------------
+    @staticmethod
+    def _node_key(ref):
+        """What two walks compare: a plain tensor by its memory, an entry that holds its tensor plainly by that tensor, any other entry by itself."""
+        if ref[0] == "entry" and ref[2].raw is not None and ref[2].delta is False:
+            ref = ("tensor", ref[2].raw)
+        if ref[0] == "tensor":
+            return ("t", ref[1].data_ptr(), ref[1].numel() * ref[1].element_size())
+        return ("e", id(ref[2]))
+
+    @classmethod
+    def _patch_path(cls, ref):
+        """Walk base links from `ref` while the entry is "sparse" or "same" -> [(node key, the patches on the way there)]: the first element is `ref` itself with
+        no patch, the last the first node that is neither (a plain tensor, or an entry with a body of its own)."""
+        path, patches = [(cls._node_key(ref), ())], []
+        while ref[0] == "entry" and ref[2].delta in ("sparse", "same"):
+            e = ref[2]
+            if e.delta == "sparse":
+                patches.append(e.patch)
+            ref = e.base
+            path.append((cls._node_key(ref), tuple(patches)))
+        return path
+
+    def rebased(self, onto):
+        """The same tensors as a NEW variant store whose base is `onto` — a ResidentCheckpoint on this store's device — without decoding what is kept as
+        "znp1" patches: patches are XOR lists, so the patch of a tensor over `onto` is the XOR-merge (zn_patch_merge_batch_dev) of the patches
+        that lie between the two.
+
+            flat = s3.rebased(base)        # a chain s3 -> s2 -> s1 -> base becomes one store directly over base
+            sw = ft_b.rebased(ft_a)        # siblings over one base: B as patches over A
+            sw.apply_(model)               # live weights that hold A's values now hold B's: one sparse pass; sw.revert_(model) goes back
+
+        Per tensor both stores' base links are walked while the entry is "sparse" or "same"; where the walks meet — the same entry, or the same plain base
+        tensor — the new patch is the merge of every patch on both paths ("same" links bring nothing; `onto` lying on this store's own path has an empty
+        side).  The pairwise merges of all tensors of a round are ONE batched call, intermediate results live in that round's scratch arena, the final patches
+        are packed at 256-byte boundaries of one allocation.  An empty merge makes the entry "same" over `onto`; a patch shorter than the tensor makes it
+        "sparse".  Every other tensor — no common node, a delta body or plain body on a path, a merged patch not smaller than the tensor, a tensor the codec
+        does not take, a name `onto` lacks or has with another dtype or shape — is decoded from this store, in groups of at most _BUILD_GROUP_BYTES, and built
+        by from_state_dict(..., base=onto, sparse=True): nothing is refused, the result is always complete.
+        A merged patch does NOT compete with the delta body the tensor might also have over `onto`: rebased keeps patches as patches.
+        The new store decodes exactly the bytes this one decodes, through every entry point; this store's recorded digests carry over unchanged.  It has no
+        index (build_index on it behaves as on any variant), keeps `onto` alive and nothing else of the old chain, and changes neither store."""
+        if not isinstance(onto, ResidentCheckpoint):
+            raise ValueError("rebased: onto is a ResidentCheckpoint")
+        if onto.device != self.device:
+            raise ValueError(f"rebased: onto is a store on {self.device}, not on {onto.device}")
+        dev, lib = self.device, _capi.lib()
+        refs = self._base_items(onto, dev)
+        lists, fallback, entries = {}, [], {}
+        for name, e in self._entries.items():
+            ref = refs.get(name)
+            rb = None if ref is None else ref[1] if ref[0] == "tensor" else ref[2]
+            ok = (rb is not None and rb.dtype == e.dtype and tuple(rb.shape) == e.shape and e.P in (1, 2, 4) and e.P == torch.empty(0, dtype=e.dtype).element_size()
+                  and 0 < e.nbytes and e.nbytes // e.P < (1 << 32))
+            if ok and ref[0] == "entry":           # (what a "same" or sparse entry can decode over: from_state_dict's delta_ok)
+                ok = rb.decoded and (rb.P, rb.bits, rb.byts, rb.chunk) == (e.P, e.bits, e.byts, e.chunk)
+            found = None
+            if ok:
+                mine, theirs = self._patch_path(("entry", self, e)), self._patch_path(("entry", onto, onto._entries[name]))
+                at = {k: ps for k, ps in reversed(theirs)}      # (the nearest occurrence of a key wins)
+                for k, ps in mine:
+                    if k in at:
+                        found = list(ps) + list(at[k])
+                        break
+            if found is None:
+                fallback.append(name)
+            else:
+                lists[name] = found
+        # rounds of pairwise merges, every tensor's in one call: a chain of depth d is d - 1 calls for the whole store
+        scratch = []                               # the rounds' arenas: intermediate patches are views of them
+        with _device_of(dev):
+            while any(len(ps) > 1 for ps in lists.values()):
+                todo = [name for name, ps in lists.items() if len(ps) > 1]
+                got = codec.patch_merge_device_batch(lib, [(lists[n][0], lists[n][1], self._entries[n].nbytes, self._entries[n].P) for n in todo])
+                scratch.append(got)
+                for n, g in zip(todo, got):
+                    lists[n] = ([g] if g is not None else []) + lists[n][2:]
+        kept = []
+        for name, ps in lists.items():
+            if ps and ps[0].numel() >= self._entries[name].nbytes:
+                fallback.append(name)              # a patch that is not smaller than the tensor: the build decides what it is kept as
+            else:
+                kept.append((name, ps[0] if ps else None))
+        offs, o = {}, 0
+        for name, p in kept:
+            if p is not None:
+                offs[name] = o
+                o += _round_up(p.numel())
+        packed = torch.empty(max(o, 1), dtype=torch.uint8, device=dev)
+        for name, p in kept:
+            e, ref = self._entries[name], refs[name]
+            prm = (e.P, e.bits, e.byts, e.chunk)
+            if p is None:
+                ne = _Entry(name, e.dtype, e.shape, e.nbytes, raw=ref[1] if ref[0] == "tensor" else None, params=prm)
+                ne.delta = "same"
+            else:
+                ne = _Entry(name, e.dtype, e.shape, e.nbytes, params=prm)
+                ne.patch = packed[offs[name]:offs[name] + p.numel()]
+                ne.patch.copy_(p)
+                ne.delta, ne.entries = "sparse", _patch_entries(e.nbytes, e.P, p.numel())
+            ne.base = ne.restore = ref
+            ne.head = e.head
+            entries[name] = ne
+        del scratch, lists
+        keep, held = [packed], o
+        order = {n: i for i, n in enumerate(self._entries)}
+        fallback.sort(key=order.__getitem__)
+        groups, cur, size = [], [], 0
+        for name in fallback:
+            nb = self._entries[name].nbytes
+            if cur and size + nb > self._BUILD_GROUP_BYTES:
+                groups.append(cur)
+                cur, size = [], 0
+            cur.append(name)
+            size += nb
+        if cur:
+            groups.append(cur)
+        for grp in groups:
+            sub = type(self).from_state_dict(self.get_tensors(grp), dev, base=onto, sparse=True)
+            entries.update(sub._entries)
+            keep += [k for k in sub._keep if k is not onto]
+            held += sub._held
+        keep.append(onto)
+        store = type(self)(dev, [entries[name] for name in self._entries], held, keep=keep)
+        store._digests = dict(self._digests) if self._digests is not None else None
+        store._metadata = self._metadata
         return store
 
     # ---- the sync index ---------------------------------------------------------------------------------------------------------
