@@ -68,8 +68,28 @@ def to_host(lib, t, out=None):
     return out
 
 
+class _nullctx:
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        return False
+
+
+def _device_of(dev):
+    """torch.cuda.device(dev) for a GPU, nothing for the emulated library's CPU tensors."""
+    return torch.cuda.device(dev) if dev.type == "cuda" else _nullctx()
+
+
+def _stream_of(dev, stream=None):
+    """-> the raw stream handle to launch on: `stream` (a torch.cuda.Stream or a handle), else the device's current stream."""
+    if stream is not None:
+        return getattr(stream, "cuda_stream", stream)
+    return torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+
+
 def _stream_handle(t):
-    return torch.cuda.current_stream(t.device).cuda_stream if t.is_cuda else 0
+    return _stream_of(t.device)
 
 
 def _delta_ptr(delta, like):
@@ -96,7 +116,7 @@ def compress_device(lib, flat, num_buf, bits_mode, bytes_mode, chunk, threshold,
         body = torch.empty(max(cap, 16), dtype=torch.uint8, device=flat.device)
     elif body.dtype != torch.uint8 or body.device != flat.device or body.numel() < max(cap, 16) or not body.is_contiguous():
         raise ValueError("body must be a contiguous uint8 tensor on the same device with at least zn_compress_bound bytes")
-    with torch.cuda.device(flat.device) if flat.is_cuda else _nullctx():
+    with _device_of(flat.device):
         used = lib.compress_dev(flat.data_ptr() if n else 0, n, num_buf, bits_mode, bytes_mode, chunk, threshold,
                                 body.data_ptr(), body.numel(), _stream_handle(flat), delta_ptr=dptr)
     return body[:used]
@@ -128,18 +148,10 @@ def decompress_device(lib, body, num_buf, bits_mode, bytes_mode, chunk, orig_siz
         return out
     body = body.contiguous()
     delta, dptr = _delta_ptr(delta, out)
-    with torch.cuda.device(body.device) if body.is_cuda else _nullctx():
+    with _device_of(body.device):
         lib.decompress_dev(body.data_ptr(), body.numel(), num_buf, bits_mode, bytes_mode, chunk, orig_size,
                            out.data_ptr(), _stream_handle(body), check, delta_ptr=dptr)
     return out
-
-
-class _nullctx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
 
 
 def decompress_device_batch(lib, items, check=True, into=None):
@@ -164,7 +176,7 @@ def decompress_device_batch(lib, items, check=True, into=None):
         outs = [into[o:o + n] for o, (_, _, _, _, _, n) in zip(offs, items)]
     else:
         outs = [torch.empty(n, dtype=torch.uint8, device=dev) for (_, _, _, _, _, n) in items]
-    with torch.cuda.device(dev) if dev.type == "cuda" else _nullctx():
+    with _device_of(dev):
         lib.decompress_batch_dev(((b.data_ptr(), b.numel(), nb, bi, by, ch, n, o.data_ptr() if n else 0,
                                    d.data_ptr() if (d is not None and n) else None)
                                   for (b, nb, bi, by, ch, n), o, d in zip(items, outs, deltas)), _stream_handle(items[0][0]), check)
@@ -194,7 +206,7 @@ def decompress_device_windows(lib, items, check=True, outs=None):
         outs = [torch.empty(sz, dtype=torch.uint8, device=dev) for sz in sizes]
     elif len(outs) != len(items) or any(o.numel() < sz or o.dtype != torch.uint8 or not o.is_contiguous() for o, sz in zip(outs, sizes)):
         raise ValueError("outs: one contiguous uint8 destination of the window's size per item")
-    with torch.cuda.device(dev) if dev.type == "cuda" else _nullctx():
+    with _device_of(dev):
         lib.decompress_window_batch_dev(((b.data_ptr(), b.numel(), nb, bi, by, ch, n, lo, hi, o.data_ptr() if sz else 0,
                                           d.data_ptr() if (d is not None and n) else None)
                                          for (b, nb, bi, by, ch, n, lo, hi, d), o, sz in zip(items, outs, sizes)), _stream_handle(items[0][0]), check)
@@ -225,7 +237,7 @@ def compress_device_batch(lib, items, gap=0, return_arena=False):
         offs.append(o); o += (c + 255) // 256 * 256
     arena = torch.empty(max(o, 16), dtype=torch.uint8, device=dev)
     base = arena.data_ptr()
-    with torch.cuda.device(dev) if dev.type == "cuda" else _nullctx():
+    with _device_of(dev):
         lens = lib.compress_batch_dev(((f.data_ptr() if f.numel() else 0, f.numel(), nb, bi, by, ch, th, base + b0, c,
                                         d.data_ptr() if (d is not None and f.numel()) else None)
                                        for (f, nb, bi, by, ch, th), c, b0, d in zip(items, caps, offs, deltas)), _stream_handle(arena))
@@ -262,7 +274,7 @@ def patch_sizes_device_batch(lib, pairs):
     if not pairs:
         return []
     dev = pairs[0][0].device
-    with torch.cuda.device(dev) if dev.type == "cuda" else _nullctx():
+    with _device_of(dev):
         return lib.patch_size_batch_dev([(s.data_ptr() if s.numel() else 0, b.data_ptr() if s.numel() else 0, s.numel(), el) for s, b, el in pairs], _stream_handle(pairs[0][0]))
 
 
@@ -283,7 +295,7 @@ def patch_build_device_batch(lib, pairs, sizes=None):
         offs.append(o)
         o += (n + 255) // 256 * 256
     arena = torch.empty(max(o, 16), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev) if dev.type == "cuda" else _nullctx():
+    with _device_of(dev):
         lens = lib.patch_build_batch_dev([(s.data_ptr() if s.numel() else 0, b.data_ptr() if s.numel() else 0, s.numel(), el, arena.data_ptr() + off, n)
                                           for (s, b, el), off, n in zip(pairs, offs, sizes)], _stream_handle(arena))
     return [arena[off:off + n] if n else None for off, n in zip(offs, lens)]
@@ -314,7 +326,7 @@ def patch_apply_(t, patch, check=True):
     if patch.dtype != torch.uint8 or patch.device != d.device or not patch.is_contiguous():
         raise ValueError("patch_apply_: the patch is a contiguous uint8 tensor on the tensor's device")
     n = d.numel() * el
-    with torch.cuda.device(d.device) if d.is_cuda else _nullctx():
+    with _device_of(d.device):
         _capi.lib().patch_apply_batch_dev([(patch.data_ptr(), patch.numel(), n, el, 0, n, d.data_ptr() if n else 0)], _stream_handle(d), check)
     return t
 
@@ -335,7 +347,7 @@ def patch_merge_sizes_device_batch(lib, triples):
     if not triples:
         return []
     dev = triples[0][0].device
-    with torch.cuda.device(dev) if dev.type == "cuda" else _nullctx():
+    with _device_of(dev):
         return lib.patch_merge_size_batch_dev([(a.data_ptr(), a.numel(), b.data_ptr(), b.numel(), n, el) for a, b, n, el in triples], _stream_handle(triples[0][0]))
 
 
@@ -354,7 +366,7 @@ def patch_merge_device_batch(lib, triples, sizes=None, return_arena=False):
         offs.append(o)
         o += (n + 255) // 256 * 256
     arena = torch.empty(max(o, 16), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev) if dev.type == "cuda" else _nullctx():
+    with _device_of(dev):
         lens = lib.patch_merge_batch_dev([(a.data_ptr(), a.numel(), b.data_ptr(), b.numel(), n, el, arena.data_ptr() + off if cap else 0, cap)
                                           for (a, b, n, el), off, cap in zip(triples, offs, sizes)], _stream_handle(arena))
     if return_arena:
@@ -406,7 +418,7 @@ def patch_check_device_batch(lib, items, stream=None):
         if p.dtype != torch.uint8 or not p.is_contiguous() or p.device != items[0][0].device:
             raise ValueError("patch: contiguous uint8 tensors on one device")
     dev = items[0][0].device
-    with torch.cuda.device(dev) if dev.type == "cuda" else _nullctx():
+    with _device_of(dev):
         return lib.patch_check_batch_dev([(p.data_ptr(), p.numel(), n, el) for p, n, el in items], stream if stream is not None else _stream_handle(items[0][0]))
 
 
@@ -457,7 +469,7 @@ def digest_device_batch(lib, flats, stream=None, out=None):
     if flats:
         if any(f.dtype != torch.uint8 or f.device != dev or not f.is_contiguous() for f in flats):
             raise ValueError("digest: contiguous uint8 tensors on one device")
-        with torch.cuda.device(dev) if dev.type == "cuda" else _nullctx():
+        with _device_of(dev):
             lib.digest_batch_dev([(f.data_ptr() if f.numel() else 0, f.numel()) for f in flats], out.data_ptr(),
                                  stream if stream is not None else _stream_handle(out))
     return out[:len(flats)]
@@ -466,6 +478,15 @@ def digest_device_batch(lib, flats, stream=None, out=None):
 def digests_to_ints(out):
     """The one read-back of a digest_device_batch result (8 bytes per item; waits for the stream) -> list of unsigned ints."""
     return [v & 0xFFFFFFFFFFFFFFFF for v in out.tolist()]
+
+
+def digests_of(lib, tensors, stream=None):
+    """Live tensors on ONE device -> their digests as ints, in order: digested where they lie by one batched launch, one read-back."""
+    tensors = list(tensors)
+    if not tensors:
+        return []
+    with _device_of(tensors[0].device):
+        return digests_to_ints(digest_device_batch(lib, [flat_bytes(t) for t in tensors], stream))
 
 
 def _host_bytes(x):

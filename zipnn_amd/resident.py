@@ -46,33 +46,123 @@ def _patch_entries(n, elem, length):
     return t
 
 
-def _stream_of(dev, stream=None):
-    """-> the raw stream handle to launch on: `stream` (a torch.cuda.Stream or a handle), else the device's current stream."""
-    if stream is not None:
-        return getattr(stream, "cuda_stream", stream)
-    return torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+def _itemsize(dtype):
+    return dtype.itemsize
 
 
-class _device_of:
-    """torch.cuda.device(dev) for a GPU, nothing for the emulated library's CPU tensors."""
+def _frame_params_for(dtype, shape, method=None, coders=None, like=None):
+    """Which frame would a tensor of this dtype and shape be coded with?  -> (the first 16 bytes of its frame header, (P, bits, byts, chunk)).
+    coders: a dict that keeps one ZipNN per dtype — what decides both — over the calls of one build; like: a tensor of that dtype and shape, where the caller has one."""
+    coders = coders if coders is not None else {}
+    if dtype not in coders:
+        coders[dtype] = ZipNN(input_format="torch", bytearray_dtype=dtype, method=method or COMPRESSION_METHOD)
+    hdr, P, bits, byts, chunk = coders[dtype].torch_frame_plan(like if like is not None else torch.empty(shape, dtype=dtype, device="meta"))
+    return bytes(hdr[:16]), (P, bits, byts, chunk)
 
-    def __init__(self, dev):
-        self._ctx = torch.cuda.device(dev) if dev.type == "cuda" else None
 
-    def __enter__(self):
-        if self._ctx is not None:
-            self._ctx.__enter__()
-        return self
+def _groups(items, size_of, limit):
+    """items, in order -> lists of them of at most `limit` bytes each by size_of(item) (a larger item makes a group of its own)."""
+    groups, cur, size = [], [], 0
+    for it in items:
+        nb = size_of(it)
+        if cur and size + nb > limit:
+            groups.append(cur)
+            cur, size = [], 0
+        cur.append(it)
+        size += nb
+    if cur:
+        groups.append(cur)
+    return groups
 
-    def __exit__(self, *a):
-        return self._ctx.__exit__(*a) if self._ctx is not None else False
+
+def _packed(sizes):
+    """-> ([offset of each], total): buffers of these sizes back to back in one allocation, each at a multiple of ALIGN."""
+    offs, o = [], 0
+    for n in sizes:
+        offs.append(o)
+        o += _round_up(n)
+    return offs, o
+
+
+def _named_tensors(target):
+    """A module (its named parameters and buffers) or a mapping of names to tensors -> {name: tensor}."""
+    if isinstance(target, torch.nn.Module):
+        items = dict(target.named_parameters())
+        items.update(dict(target.named_buffers()))
+        return items
+    return dict(target)
+
+
+_stream_of, _device_of = codec._stream_of, codec._device_of
+
+# The kinds of launch set (_launch_sets) and the ZnLib methods that serve each: (the batched call, plan create, plan run, plan destroy)
+_KINDS = {"window": ("decompress_window_batch_dev", "plan_create", "plan_run", "plan_destroy"),
+          "hinted": ("decompress_hinted_batch_dev", "plan_create_hinted", "plan_run", "plan_destroy"),
+          "patch": ("patch_apply_batch_dev", "patch_plan_create", "patch_plan_run", "patch_plan_destroy")}
+
+
+def _launch(lib, steps, stream, check):
+    """steps: [(call, its items or plan handle, _)], launched in order on `stream`.  check=False: the steps behind the first add their verdict to the first's
+    (zn_decode_status_chain), so that one decode_status speaks for the whole run."""
+    chain = len(steps) > 1 and not check
+    try:
+        for i, (call, arg, _) in enumerate(steps):
+            if i == 1 and chain:
+                lib.decode_status_chain(True)
+            call(arg, stream, check)
+    finally:
+        if chain:
+            lib.decode_status_chain(False)
+
+
+class _BaseRef:
+    """One tensor of a variant's base — what an entry decodes over (_Entry.base) and what revert_ restores from (_Entry.restore): a tensor that lies plainly
+    on the device (`tensor`, held by reference and read where it lies), or an entry of a resident store (`store`, `entry`) that is decoded through that store."""
+    __slots__ = ("tensor", "store", "entry")
+
+    def __init__(self, tensor=None, store=None, entry=None):
+        self.tensor, self.store, self.entry = tensor, store, entry
+
+    @property
+    def dtype(self):
+        return (self.tensor if self.tensor is not None else self.entry).dtype
+
+    @property
+    def shape(self):
+        return tuple((self.tensor if self.tensor is not None else self.entry).shape)
+
+    def fits(self, dtype, shape):
+        """Does the base hold this tensor with this dtype and shape?"""
+        return self.dtype == dtype and self.shape == tuple(shape)
+
+    def params(self, coders=None):
+        """-> the frame parameters (P, bits, byts, chunk) the base tensor is coded with, or would be (coders: see _frame_params_for)."""
+        if self.entry is not None:
+            return (self.entry.P, self.entry.bits, self.entry.byts, self.entry.chunk)
+        return _frame_params_for(self.dtype, self.shape, coders=coders, like=self.tensor)[1]
+
+    def decodes_under(self, params, coders=None):
+        """Can a delta body, a "same" or a sparse entry with these frame parameters decode over it?  A resident base decodes in its own chunks."""
+        return (self.entry is None or self.entry.decoded) and self.params(coders) == tuple(params)
+
+    @property
+    def key(self):
+        """What two walks of base links compare: a plain tensor by its memory, an entry that holds its tensor plainly by that tensor, any other entry by itself."""
+        t = self.tensor
+        if t is None and self.entry.raw is not None and self.entry.delta is False:
+            t = self.entry.raw
+        return ("t", t.data_ptr(), t.numel() * t.element_size()) if t is not None else ("e", id(self.entry))
+
+    def flat(self):
+        """-> the plain tensor's bytes where they lie, or None: the base holds the tensor compressed and it must be decoded."""
+        return codec.flat_bytes(self.tensor) if self.tensor is not None else None
 
 
 class _Entry:
     """One tensor of the store: a frame body in device memory (`body`, with its codec parameters), or the tensor itself (`raw`).
     In a variant store (ResidentCheckpoint.from_state_dict(..., base=...)): `delta` is True where the body encodes tensor ^ base, "same" where the tensor's
     bytes are the base's (no body; `raw` is the base's own tensor where the base holds it plainly) and False otherwise; `base` is what a delta or "same" entry
-    decodes over and `restore` what revert_ puts back — ("tensor", the base's tensor, held by reference) or ("entry", the base store, its entry) — or None.
+    decodes over and `restore` what revert_ puts back — a _BaseRef (the base's tensor, held by reference, or the base store and its entry) — or None.
     `head`: the first 16 bytes of the frame header the body was written behind or would be (magic … dtype code): what save_file writes in front of it again.
     A SPARSE entry (from_state_dict(..., base=..., sparse=True)): `delta` is "sparse", there is no body, `patch` is the "znp1" patch
     (include/zipnn_hip.h) that turns the base's bytes into the tensor's and `entries` its number of elements; reading it is the base's bytes with the patch
@@ -86,6 +176,36 @@ class _Entry:
         self.delta, self.base, self.restore = False, None, None
         self.head = None
         self.patch, self.entries = None, 0
+
+    # the four kinds of entry (head: see above; the constructors below are the only places that set delta, base, patch and entries)
+    @classmethod
+    def framed(cls, name, dtype, shape, nbytes, body, params, head=None, base=None):
+        """A frame body of its own: the tensor's, or (base: a _BaseRef) that of tensor ^ base."""
+        e = cls(name, dtype, shape, nbytes, body=body, params=params)
+        e.head, e.delta, e.base = head, base is not None, base
+        return e
+
+    @classmethod
+    def held(cls, name, raw, head=None):
+        """The tensor itself."""
+        e = cls(name, raw.dtype, raw.shape, raw.numel() * raw.element_size(), raw=raw)
+        e.head = head
+        return e
+
+    @classmethod
+    def same(cls, name, dtype, shape, ref, params, head=None):
+        """Nothing of its own: the base's tensor itself, or a decode of the base's body."""
+        e = cls(name, dtype, shape, _numel(shape) * _itemsize(dtype), raw=ref.tensor, params=params)
+        e.head, e.delta, e.base = head, "same", ref
+        return e
+
+    @classmethod
+    def sparse(cls, name, dtype, shape, ref, params, patch, head=None):
+        """A "znp1" patch over the base's bytes; params: the frame parameters the tensor would be coded with."""
+        e = cls(name, dtype, shape, _numel(shape) * _itemsize(dtype), params=params)
+        e.head, e.delta, e.base, e.patch = head, "sparse", ref, patch
+        e.entries = _patch_entries(e.nbytes, e.P, patch.numel())
+        return e
 
     @property
     def compressed(self):
@@ -205,10 +325,10 @@ class ResidentCheckpoint:
         upload and before anything is decoded, ONE zn_patch_check_batch_dev call validates every patch whole (header, first[], every entry, padding); a ValueError
         names every damaged tensor with its mask.  check_patches=False skips both; apply's own checks remain.  A well-formed patch of ANOTHER tensor passes:
         verify=True (the digests) is what catches that."""
-        import json
         from . import safetensors_io
         dev = cls._work_device(device)
-        meta = safetensors_io.read_metadata(path)
+        lay = safetensors_io._read_layout(path)                        # (the container's header, read once: the metadata, and what the patches' check and the upload go by)
+        meta = lay[0] if lay is not None else safetensors_io.read_metadata(path)
         recorded = safetensors_io.file_digests(meta) if (digests or verify) else None
         if verify and recorded is None:
             raise ValueError(f"{path}: the file carries no digests (znn_digests): nothing to verify against")
@@ -219,97 +339,20 @@ class ResidentCheckpoint:
         kinds, over = {}, {}                                           # {name: "delta" | "same" | "sparse"}, {name: (dtype, shape, what it is coded over)}
         if delta is not None:
             kinds, want = delta
-            infos = safetensors_io.get_compressed_tensors_metadata(meta)
-            for name in kinds:
-                if name not in infos:
-                    raise ValueError(f"{path}: {name!r} is listed under znn_delta but not under znn_compressed_vectors")
-                dt, shape = getattr(torch, str(infos[name].get("dtype")), None), tuple(int(d) for d in json.loads(infos[name].get("shape", "[]")))
-                if not isinstance(dt, torch.dtype):
-                    raise ValueError(f"{path}: {name!r}: unknown dtype {infos[name].get('dtype')!r}")
-                ref = based.get(name)
-                if ref is None:
-                    raise ValueError(f"{path}: the base has no tensor {name!r}, which the file codes over it")
-                b = ref[1] if ref[0] == "tensor" else ref[2]
-                if b.dtype != dt or tuple(b.shape) != shape:
-                    raise ValueError(f"{path}: {name!r} is {dt} {list(shape)} over a base tensor of the same dtype and shape; the base holds {b.dtype} {list(b.shape)}")
-                over[name] = (dt, shape, ref)
+            over = safetensors_io._delta_over_base(path, meta, kinds, based)
             if verify_base:
                 got = cls._ref_digests({name: ref for name, (_, _, ref) in over.items()}, dev)
                 bad = [name for name in kinds if got[name] != want[name]]
                 if bad:
                     raise codec.DigestMismatch(bad, f"{path}: the base does not hold what the delta was taken over")
-        patched = cls._file_patches(path, {n: over[n] for n, k in kinds.items() if k == "sparse"}, check_patches)      # {name: (offset in the data section, L, T, elem)}
-        up = safetensors_io._upload_file(path, dev, delta=delta is not None)
-        if up is None:
+        if lay is None:
             raise ValueError(f"{path}: the container names a dtype this loader does not know")
-        layout, plan, blob = up.layout, up.frames, up.blob
-        entries, framed, extra = [], {}, 0
-        for (name, b0, hi, fp, _) in plan:
-            _, P, bits, byts, chunk, n, tdt, shape = fp
-            head = up.heads.get(name)
-            is_delta = kinds.get(name) == "delta"
-            if head is not None and (head[9] != 0) != is_delta:
-                raise ValueError(f"{path}: {name!r}: the frame header says {'delta' if head[9] else 'no delta'}, znn_delta says otherwise")
-            if is_delta:
-                tdt, shape, ref = over[name]
-                if n != _numel(shape) * torch.empty(0, dtype=tdt).element_size():
-                    raise ValueError(f"{path}: {name!r}: a frame of {n} bytes for {tdt} {list(shape)}")
-                if ref[0] == "entry" and ref[2].chunk != chunk:
-                    raise ValueError(f"{path}: {name!r} is coded in chunks of {chunk} bytes, the base holds it in chunks of {ref[2].chunk}")
-            e = framed[name] = _Entry(name, tdt, shape if shape is not None else (n // max(torch.empty(0, dtype=tdt).element_size(), 1),), n,
-                                      body=blob[b0:hi], params=(P, bits, byts, chunk))
-            e.head = head
-            if is_delta:
-                e.delta, e.base = True, ref
-        for name, (dt, shape, lo, hi) in layout.items():          # (file order)
-            if name in framed:
-                entries.append(framed[name])
-                continue
-            if kinds.get(name) == "same":                          # nothing of its own: the base's tensor itself, or a decode of the base's body
-                tdt, tshape, ref = over[name]
-                if hi != lo:
-                    raise ValueError(f"{path}: {name!r} is listed as \"same\" but holds {hi - lo} bytes")
-                if ref[0] == "tensor":
-                    params = tuple(ZipNN(input_format="torch", bytearray_dtype=tdt, method=COMPRESSION_METHOD).torch_frame_plan(torch.empty(tshape, dtype=tdt, device="meta"))[1:])
-                else:
-                    params = (ref[2].P, ref[2].bits, ref[2].byts, ref[2].chunk)
-                e = _Entry(name, tdt, tshape, _numel(tshape) * torch.empty(0, dtype=tdt).element_size(), raw=ref[1] if ref[0] == "tensor" else None, params=params)
-                e.delta, e.base = "same", ref
-                entries.append(e)
-                continue
-            if kinds.get(name) == "sparse":                        # the patch where the upload put it; the frame parameters the tensor would be coded with
-                tdt, tshape, ref = over[name]
-                at, L, T, elem = patched[name]
-                if ref[0] == "tensor":
-                    params = tuple(ZipNN(input_format="torch", bytearray_dtype=tdt, method=COMPRESSION_METHOD).torch_frame_plan(torch.empty(tshape, dtype=tdt, device="meta"))[1:])
-                else:
-                    params = (ref[2].P, ref[2].bits, ref[2].byts, ref[2].chunk)
-                if params[0] != elem:
-                    raise ValueError(f"{path}: {name!r}: {tdt} is not a dtype a patch describes")
-                e = _Entry(name, tdt, tshape, _numel(tshape) * elem, params=params)
-                e.patch, e.delta, e.base, e.entries = blob[at:at + L], "sparse", ref, T
-                if e.patch.data_ptr() % 16:                        # (the upload's allocation is aligned far beyond 16 bytes; should one not be, the apply kernel still needs it)
-                    e.patch = e.patch.clone()
-                    extra += L
-                entries.append(e)
-                continue
-            if hi > lo:
-                es = torch.empty(0, dtype=dt).element_size()
-                raw = blob[lo:hi]
-                if (blob.data_ptr() + lo) % max(es, 1):            # (a view needs the element's alignment: safetensors does not promise it)
-                    raw = raw.clone()
-                    extra += hi - lo
-                raw = raw.view(dt).reshape(shape)
-            else:
-                raw = torch.empty(shape, dtype=dt, device=dev)
-            entries.append(_Entry(name, dt, shape, hi - lo, raw=raw))
-        for e in entries:                                          # what revert_ restores from: the base's tensor of the same name, dtype and shape
-            ref = based.get(e.name)
-            if ref is not None:
-                b = ref[1] if ref[0] == "tensor" else ref[2]
-                if b.dtype == e.dtype and tuple(b.shape) == e.shape:
-                    e.restore = ref
-        store = cls(dev, entries, blob.numel() + extra, keep=(blob,) + ((base,) if base is not None else ()))
+        patched = safetensors_io._read_sparse_entries(path, lay, {n: over[n][:2] for n, k in kinds.items() if k == "sparse"}, check_patches)
+        up = safetensors_io._upload_file(path, dev, delta=delta is not None, lay=lay)
+        framed = cls._file_frames(path, up, kinds, over)
+        entries, extra = cls._file_entries(path, up, framed, kinds, over, patched)
+        cls._link_restore(entries, based)
+        store = cls(dev, entries, up.blob.numel() + extra, keep=(up.blob,) + ((base,) if base is not None else ()))
         store._metadata = {k: v for k, v in up.metadata.items() if k not in (safetensors_io.METADATA_KEY, safetensors_io.DIGESTS_KEY, safetensors_io.DELTA_KEY)}
         if patched and check_patches:                              # before anything is decoded: every patch whole, one launch, one read-back
             sp = [e for e in entries if e.patch is not None]
@@ -331,58 +374,81 @@ class ResidentCheckpoint:
         return store
 
     @staticmethod
-    def _file_patches(path, over, check_slack):
-        """The "sparse" entries of a delta file, from the file alone, before anything is uploaded.  over: {name: (dtype, shape, _)} -> {name: (offset of the patch
-        in the data section, L, T, elem)}.  The patch starts at the entry's first multiple of 16; its header must describe the tensor and give the
-        entry's length; check_slack: the up to 15 bytes of the entry around the patch must be zero.  A ValueError names the tensor."""
-        if not over:
-            return {}
-        from . import safetensors_io
-        lay = safetensors_io._read_layout(path)
-        if lay is None:
-            raise ValueError(f"{path}: the container names a dtype this loader does not know")
-        _, layout, data_start = lay
-        lib, out = _capi.lib(), {}
-        with open(path, "rb") as f:
-            for name, (dt, shape, _) in over.items():
-                fdt, _, lo, hi = layout[name]
-                elem = torch.empty(0, dtype=dt).element_size()
-                n = _numel(shape) * elem
-                at = (lo + 15) // 16 * 16
-                if fdt != torch.uint8 or hi - lo < 32 + safetensors_io.SPARSE_SLACK:
-                    raise ValueError(f"{path}: {name!r} is listed as \"sparse\" but its entry of {hi - lo} bytes cannot hold a patch")
-                f.seek(data_start + lo)
-                head = f.read(at - lo + 32)
-                magic, E, T, L = head[at - lo: at - lo + 4], head[at - lo + 4], int.from_bytes(head[at - lo + 16: at - lo + 24], "little"), int.from_bytes(head[at - lo + 24: at - lo + 32], "little")
-                if magic != b"ZNP1" or E != elem or int.from_bytes(head[at - lo + 8: at - lo + 16], "little") != n:
-                    raise ValueError(f"{path}: {name!r}: the patch's header does not describe a {dt} tensor of {n} bytes")
-                if hi - lo != L + safetensors_io.SPARSE_SLACK:
-                    raise ValueError(f"{path}: {name!r}: an entry of {hi - lo} bytes for a patch of {L} (the entry is the patch and {safetensors_io.SPARSE_SLACK} bytes)")
-                if T > n // elem or lib.patch_len(n, elem, T) != L:
-                    raise ValueError(f"{path}: {name!r}: {L} bytes is not the length of a patch of {T} elements")
-                if check_slack:
-                    f.seek(data_start + at + L)
-                    if any(head[:at - lo]) or any(f.read(hi - at - L)):
-                        raise ValueError(f"{path}: {name!r}: the bytes around the patch are not zero")
-                out[name] = (at, L, T, elem)
-        return out
+    def _file_frames(path, up, kinds, over):
+        """from_file, the frames of an uploaded file -> {name: entry}: bodies that are views of the data section; a delta body's against what it is coded over."""
+        framed = {}
+        for (name, b0, hi, fp, _) in up.frames:
+            _, P, bits, byts, chunk, n, tdt, shape = fp
+            head = up.heads.get(name)
+            ref = None
+            is_delta = kinds.get(name) == "delta"
+            if head is not None and (head[9] != 0) != is_delta:
+                raise ValueError(f"{path}: {name!r}: the frame header says {'delta' if head[9] else 'no delta'}, znn_delta says otherwise")
+            if is_delta:
+                tdt, shape, ref = over[name]
+                if n != _numel(shape) * _itemsize(tdt):
+                    raise ValueError(f"{path}: {name!r}: a frame of {n} bytes for {tdt} {list(shape)}")
+                if ref.entry is not None and ref.entry.chunk != chunk:
+                    raise ValueError(f"{path}: {name!r} is coded in chunks of {chunk} bytes, the base holds it in chunks of {ref.entry.chunk}")
+            framed[name] = _Entry.framed(name, tdt, shape if shape is not None else (n // max(_itemsize(tdt), 1),), n, up.blob[b0:hi], (P, bits, byts, chunk),
+                                         head=head, base=ref)
+        return framed
+
+    @staticmethod
+    def _file_entries(path, up, framed, kinds, over, patched):
+        """from_file, every tensor of an uploaded file in file order -> ([entry], bytes held beside the data section): the frames, the "same" and sparse entries of a
+        delta file (patched: safetensors_io._read_sparse_entries), the plain tensors as views of the data section."""
+        blob, entries, extra = up.blob, [], 0
+        for name, (dt, shape, lo, hi) in up.layout.items():
+            if name in framed:
+                e = framed[name]
+            elif kinds.get(name) == "same":
+                tdt, tshape, ref = over[name]
+                if hi != lo:
+                    raise ValueError(f"{path}: {name!r} is listed as \"same\" but holds {hi - lo} bytes")
+                e = _Entry.same(name, tdt, tshape, ref, ref.params())
+            elif kinds.get(name) == "sparse":                      # the patch where the upload put it; the frame parameters the tensor would be coded with
+                tdt, tshape, ref = over[name]
+                at, L, elem = patched[name]
+                params = ref.params()
+                if params[0] != elem:
+                    raise ValueError(f"{path}: {name!r}: {tdt} is not a dtype a patch describes")
+                patch = blob[at:at + L]
+                if patch.data_ptr() % 16:                          # (the upload's allocation is aligned far beyond 16 bytes; should one not be, the apply kernel still needs it)
+                    patch = patch.clone()
+                    extra += L
+                e = _Entry.sparse(name, tdt, tshape, ref, params, patch)
+            elif hi > lo:
+                raw = blob[lo:hi]
+                if (blob.data_ptr() + lo) % max(_itemsize(dt), 1):     # (a view needs the element's alignment: safetensors does not promise it)
+                    raw = raw.clone()
+                    extra += hi - lo
+                e = _Entry.held(name, raw.view(dt).reshape(shape))
+            else:
+                e = _Entry.held(name, torch.empty(shape, dtype=dt, device=up.device))
+            entries.append(e)
+        return entries, extra
+
+    @staticmethod
+    def _link_restore(entries, based):
+        """What revert_ restores each entry from: the base's tensor of the same name, dtype and shape.  based: _base_items."""
+        for e in entries:
+            ref = based.get(e.name)
+            e.restore = ref if ref is not None and ref.fits(e.dtype, e.shape) else None
 
     @staticmethod
     def _ref_digests(refs, dev):
-        """{name: ("tensor", tensor) | ("entry", store, entry)} (_base_items) -> {name: digest of that base tensor's bytes}: a base store's recorded digest where
-        it has one; otherwise the plain tensors digested where they lie, all in one batched launch, and a store's entries through one _decoded_digests call."""
+        """{name: _BaseRef} (_base_items) -> {name: digest of that base tensor's bytes}: a base store's recorded digest where it has one; otherwise the plain
+        tensors digested where they lie, all in one batched launch, and a store's entries through one _decoded_digests call."""
         out, live, via = {}, [], {}
         for name, ref in refs.items():
-            if ref[0] == "tensor":
-                live.append((name, ref[1]))
-            elif ref[1]._digests is not None:
-                out[name] = ref[1]._digests[ref[2].name]
+            if ref.tensor is not None:
+                live.append((name, ref.tensor))
+            elif ref.store._digests is not None:
+                out[name] = ref.store._digests[ref.entry.name]
             else:
-                via.setdefault(id(ref[1]), (ref[1], []))[1].append((name, ref[2].name))
-        if live:
-            with _device_of(dev):
-                vals = codec.digests_to_ints(codec.digest_device_batch(_capi.lib(), [codec.flat_bytes(t) for _, t in live], _stream_of(dev)))
-            out.update({name: v for (name, _), v in zip(live, vals)})
+                via.setdefault(id(ref.store), (ref.store, []))[1].append((name, ref.entry.name))
+        out.update(zip([name for name, _ in live], codec.digests_of(_capi.lib(), [t for _, t in live], _stream_of(dev))))
         for bstore, pairs in via.values():
             got = bstore._decoded_digests([bn for _, bn in pairs])
             out.update({name: got[bn] for name, bn in pairs})
@@ -390,24 +456,19 @@ class ResidentCheckpoint:
 
     @staticmethod
     def _base_items(base, dev):
-        """-> {name: ("tensor", tensor) | ("entry", store, entry)} for what from_state_dict accepts as `base`."""
+        """-> {name: _BaseRef} for what from_state_dict accepts as `base`."""
         if base is None:
             return {}
         if isinstance(base, ResidentCheckpoint):
             if base.device != dev:
                 raise ValueError(f"base: a store on {dev}, not on {base.device}")
-            return {name: (("tensor", e.raw) if e.raw is not None else ("entry", base, e)) for name, e in base._entries.items()}
-        if isinstance(base, torch.nn.Module):
-            items = dict(base.named_parameters())
-            items.update(dict(base.named_buffers()))
-        else:
-            items = dict(base)
+            return {name: (_BaseRef(tensor=e.raw) if e.raw is not None else _BaseRef(store=base, entry=e)) for name, e in base._entries.items()}
         out = {}
-        for name, t in items.items():
+        for name, t in _named_tensors(base).items():
             t = t.detach()
             if t.device != dev or not t.is_contiguous():
                 raise ValueError(f"base[{name!r}]: a contiguous tensor on {dev} (plain base tensors are read where they lie)")
-            out[name] = ("tensor", t)
+            out[name] = _BaseRef(tensor=t)
         return out
 
     #: from_state_dict(base=...): base tensors are taken (and a resident base decoded) in groups of at most this many bytes
@@ -439,162 +500,142 @@ class ResidentCheckpoint:
         dev = cls._work_device(device)
         lib = _capi.lib()
         based = cls._base_items(base, dev)
-        todo, entries = [], {}
         coders = {}                            # one ZipNN per dtype: what decides a tensor's frame parameters
-
-        heads = {}                             # {name: the first 16 bytes of the frame header that describes the tensor's body}
-
-        def frame_plan(t):
-            if t.dtype not in coders:
-                coders[t.dtype] = ZipNN(input_format="torch", bytearray_dtype=t.dtype, method=method or COMPRESSION_METHOD)
-            return coders[t.dtype].torch_frame_plan(t)
-
-        def frame_params(t):
-            return tuple(frame_plan(t)[1:])
-        for name, t in sd.items():
+        todo, entries, heads = [], {}, {}      # [(name, the tensor on dev, its frame parameters)]: what the codec takes; {name: entry}; {name: _Entry.head}
+        for name, t in sd.items():             # classify: what the codec takes, and what stays as it is
             t = t.detach()
             if torch.is_floating_point(t) and t.dtype != torch.float64 and t.numel() > 0 and dtype_from_user(t.dtype) is not None:
-                hdr, P, bits, byts, chunk = frame_plan(t)
-                heads[name] = bytes(hdr[:16])
-                todo.append((name, t.to(dev), (P, bits, byts, chunk)))
+                heads[name], prm = _frame_params_for(t.dtype, t.shape, method, coders, like=t)
+                todo.append((name, t.to(dev), prm))
             else:
-                entries[name] = _Entry(name, t.dtype, t.shape, t.numel() * t.element_size(), raw=t.to(dev).clone())
-
-        def matches(name, t):                  # the base has this tensor: what revert_ restores from
-            ref = based.get(name)
-            if ref is None:
-                return None
-            b = ref[1] if ref[0] == "tensor" else ref[2]
-            return ref if (b.dtype == t.dtype and tuple(b.shape) == tuple(t.shape)) else None
-
-        def delta_ok(ref, t, prm):             # … with the same frame parameters: what a delta body can be coded over
-            if ref[0] == "tensor":
-                return frame_params(ref[1]) == tuple(prm)
-            be = ref[2]
-            return be.decoded and (be.P, be.bits, be.byts, be.chunk) == tuple(prm)
-
-        def trimmed(bodies):                   # (out of the compress arena, which is as large as the tensors themselves)
-            return [b.clone() for b in bodies]
-
+                entries[name] = _Entry.held(name, t.to(dev).clone())
         recorded = None
         if digests:                            # (the sources, before compression; raw entries are digested too)
             src = {name: t for name, t, _ in todo}
             src.update({name: e.raw for name, e in entries.items()})
-            order = list(sd.keys())
-            with _device_of(dev):
-                recorded = dict(zip(order, codec.digests_to_ints(codec.digest_device_batch(lib, [codec.flat_bytes(src[n]) for n in order]))))
+            recorded = dict(zip(sd.keys(), codec.digests_of(lib, [src[n] for n in sd.keys()])))
         keep, held = [], 0
         if todo:
-            with _device_of(dev):
-                plain = trimmed(codec.compress_device_batch(lib, [(codec.flat_bytes(t), P, bits, byts, chunk, float(threshold)) for (_, t, (P, bits, byts, chunk)) in todo]))
-                refs = [matches(name, t) for (name, t, _) in todo]
-                cand = [i for i, ((name, t, prm), ref) in enumerate(zip(todo, refs)) if ref is not None and delta_ok(ref, t, prm)]
-                dbody, same, pbody = {}, set(), {}
-                # in groups of at most _BUILD_GROUP_BYTES of base bytes: plain base tensors are read where they lie, a resident base's tensors are decoded
-                # a group at a time (never the whole base at once), the group's "is it the base's bytes" flags come back in one read
-                groups, cur, size = [], [], 0
-                for i in cand:
-                    nb = todo[i][1].numel() * todo[i][1].element_size()
-                    if cur and size + nb > cls._BUILD_GROUP_BYTES:
-                        groups.append(cur)
-                        cur, size = [], 0
-                    cur.append(i)
-                    size += nb
-                if cur:
-                    groups.append(cur)
-                for grp in groups:
-                    via = [todo[i][0] for i in grp if refs[i][0] == "entry"]
-                    decoded = base.get_tensors(via) if via else {}
-                    flats = {i: codec.flat_bytes(refs[i][1] if refs[i][0] == "tensor" else decoded[todo[i][0]]) for i in grp}
-                    eq = torch.stack([(codec.flat_bytes(todo[i][1]) == flats[i]).all() for i in grp]).tolist()
-                    same.update(i for i, e in zip(grp, eq) if e)
-                    rest = [i for i in grp if i not in same]
-                    if rest:
-                        got = trimmed(codec.compress_device_batch(lib, [(codec.flat_bytes(todo[i][1]),) + tuple(todo[i][2]) + (float(threshold), flats[i]) for i in rest]))
-                        dbody.update(zip(rest, got))
-                    if sparse and rest:                # the count pass gives every patch's length; only those below the best body so far are built
-                        elig = [i for i in rest if codec.patch_elem(todo[i][1]) == todo[i][2][0]]
-                        pairs = [(codec.flat_bytes(todo[i][1]), flats[i], todo[i][2][0]) for i in elig]
-                        sizes = codec.patch_sizes_device_batch(lib, pairs)
-                        take = [k for k, i in enumerate(elig) if 0 < sizes[k] < min(plain[i].numel(), dbody[i].numel(), flats[i].numel())]
-                        built = codec.patch_build_device_batch(lib, [pairs[k] for k in take], [sizes[k] for k in take])
-                        pbody.update({elig[k]: b.clone() for k, b in zip(take, built)})
-                    del flats, decoded
-            kept = []                              # (index, body, is a delta body)
+            refs = [based.get(name) for name, _, _ in todo]        # the base has this tensor: what a delta can be coded over (and revert_ restores from)
+            refs = [ref if ref is not None and ref.fits(t.dtype, t.shape) else None for ref, (_, t, _) in zip(refs, todo)]
+            with _device_of(dev):                      # the plain pass, then the candidates over the base
+                plain = [b.clone() for b in codec.compress_device_batch(lib, [(codec.flat_bytes(t),) + prm + (float(threshold),) for (_, t, prm) in todo])]      # (clones: out of the compress arena, which is as large as the tensors themselves)
+                cand = [i for i, ((_, _, prm), ref) in enumerate(zip(todo, refs)) if ref is not None and ref.decodes_under(prm, coders)]
+                dbody, same, pbody = cls._over_base(lib, todo, refs, cand, plain, base, float(threshold), sparse)
+            kept = cls._choose(todo, plain, dbody, same, pbody)
+            bodies, packed, o = cls._pack([b for _, b, _ in kept], dev)      # pack: the kept bodies and patches into the store's one allocation
+            for (i, _, kind), body in zip(kept, bodies):
+                name, t, prm = todo[i]
+                if kind == "sparse":
+                    entries[name] = _Entry.sparse(name, t.dtype, t.shape, refs[i], prm, body, head=heads[name])
+                else:
+                    entries[name] = _Entry.framed(name, t.dtype, t.shape, t.numel() * t.element_size(), body, prm, head=heads[name], base=refs[i] if kind else None)
             for i, (name, t, prm) in enumerate(todo):
                 if i in same:
-                    continue
-                b, is_delta = plain[i], False
-                if i in dbody and dbody[i].numel() < b.numel():        # (a tie goes to the plain body)
-                    b, is_delta = dbody[i], True
-                if i in pbody and pbody[i].numel() < min(b.numel(), t.numel() * t.element_size()):      # (… and the patch only when it is smaller than either)
-                    b, is_delta = pbody[i], "sparse"
-                if b.numel() < t.numel() * t.element_size():
-                    kept.append((i, b, is_delta))
-            offs, o = [], 0
-            for (_, b, _) in kept:
-                offs.append(o)
-                o += _round_up(b.numel())
-            packed = torch.empty(max(o, 1), dtype=torch.uint8, device=dev)
-            for (i, b, is_delta), off in zip(kept, offs):
-                name, t, prm = todo[i]
-                packed[off:off + b.numel()].copy_(b)
-                if is_delta == "sparse":
-                    e = entries[name] = _Entry(name, t.dtype, t.shape, t.numel() * t.element_size(), params=prm)
-                    e.patch, e.delta, e.base = packed[off:off + b.numel()], "sparse", refs[i]
-                    e.entries = _patch_entries(e.nbytes, e.P, b.numel())
-                    continue
-                e = entries[name] = _Entry(name, t.dtype, t.shape, t.numel() * t.element_size(), body=packed[off:off + b.numel()], params=prm)
-                if is_delta:
-                    e.delta, e.base = True, refs[i]
-            for i, (name, t, prm) in enumerate(todo):
-                if i in same:                      # nothing of its own: the base's tensor itself, or a decode of the base's body
-                    ref = refs[i]
-                    e = entries[name] = _Entry(name, t.dtype, t.shape, t.numel() * t.element_size(), raw=ref[1] if ref[0] == "tensor" else None, params=prm)
-                    e.delta, e.base = "same", ref
+                    entries[name] = _Entry.same(name, t.dtype, t.shape, refs[i], prm, head=heads[name])
                 elif name not in entries:
-                    entries[name] = _Entry(name, t.dtype, t.shape, t.numel() * t.element_size(), raw=t.clone())
-            for (name, t, _), ref in zip(todo, refs):
-                entries[name].restore = ref
+                    entries[name] = _Entry.held(name, t.clone(), head=heads[name])
             keep.append(packed)
             held += o
             del plain, dbody, pbody            # (the bodies not kept go back to the allocator)
-        for name, t in sd.items():
-            if entries[name].restore is None:
-                entries[name].restore = matches(name, t.detach())
+        cls._link_restore(entries.values(), based)                     # finish: restore links, what the store holds, digests, index
         held += sum(e.nbytes for e in entries.values() if not e.compressed and e.delta not in ("same", "sparse"))
         if base is not None:
             keep.append(base)
-        for name, h in heads.items():
-            entries[name].head = h
         store = cls(dev, [entries[name] for name in sd.keys()], held, keep=keep)
         store._digests = recorded
         if index:
             store.build_index(deltas=(index == "deltas"))
         return store
 
+    @classmethod
+    def _over_base(cls, lib, todo, refs, cand, plain, base, threshold, sparse):
+        """from_state_dict, the candidates over the base.  cand: the indices into todo whose refs[i] a delta can be coded over -> ({i: delta body}, {i: its bytes
+        ARE the base's}, {i: patch}), every body a trimmed copy out of its arena.  In groups of at most _BUILD_GROUP_BYTES of base bytes: plain base tensors are
+        read where they lie, a resident base's tensors are decoded a group at a time (never the whole base at once), the group's "is it the base's bytes" flags
+        come back in one read."""
+        dbody, same, pbody = {}, set(), {}
+        for grp in _groups(cand, lambda i: todo[i][1].numel() * todo[i][1].element_size(), cls._BUILD_GROUP_BYTES):
+            via = [todo[i][0] for i in grp if refs[i].tensor is None]
+            decoded = base.get_tensors(via) if via else {}
+            flats = {i: refs[i].flat() if refs[i].tensor is not None else codec.flat_bytes(decoded[todo[i][0]]) for i in grp}
+            eq = torch.stack([(codec.flat_bytes(todo[i][1]) == flats[i]).all() for i in grp]).tolist()
+            same.update(i for i, e in zip(grp, eq) if e)
+            rest = [i for i in grp if i not in same]
+            if rest:
+                got = [b.clone() for b in codec.compress_device_batch(lib, [(codec.flat_bytes(todo[i][1]),) + tuple(todo[i][2]) + (threshold, flats[i]) for i in rest])]
+                dbody.update(zip(rest, got))               # (clones: the group's compress arena goes back before the patches are built)
+            if sparse and rest:                # the count pass gives every patch's length; only those below the best body so far are built
+                elig = [i for i in rest if codec.patch_elem(todo[i][1]) == todo[i][2][0]]
+                pairs = [(codec.flat_bytes(todo[i][1]), flats[i], todo[i][2][0]) for i in elig]
+                sizes = codec.patch_sizes_device_batch(lib, pairs)
+                take = [k for k, i in enumerate(elig) if 0 < sizes[k] < min(plain[i].numel(), dbody[i].numel(), flats[i].numel())]
+                built = codec.patch_build_device_batch(lib, [pairs[k] for k in take], [sizes[k] for k in take])
+                pbody.update({elig[k]: b.clone() for k, b in zip(take, built)})
+            del flats, decoded
+        return dbody, same, pbody
+
+    @staticmethod
+    def _choose(todo, plain, dbody, same, pbody):
+        """from_state_dict, what each tensor is kept as -> [(index into todo, body, False | True: a delta body | "sparse": a patch)] for those that keep a body
+        smaller than the tensor."""
+        kept = []
+        for i, (name, t, prm) in enumerate(todo):
+            if i in same:
+                continue
+            b, kind = plain[i], False
+            if i in dbody and dbody[i].numel() < b.numel():        # (a tie goes to the plain body)
+                b, kind = dbody[i], True
+            if i in pbody and pbody[i].numel() < min(b.numel(), t.numel() * t.element_size()):      # (… and the patch only when it is smaller than either)
+                b, kind = pbody[i], "sparse"
+            if b.numel() < t.numel() * t.element_size():
+                kept.append((i, b, kind))
+        return kept
+
+    @staticmethod
+    def _pack(bodies, dev):
+        """-> ([copies of the bodies: views of the allocation], ONE new allocation that holds them at 256-byte boundaries, its bytes in use)."""
+        offs, o = _packed(b.numel() for b in bodies)
+        packed = torch.empty(max(o, 1), dtype=torch.uint8, device=dev)
+        views = [packed[off:off + b.numel()] for off, b in zip(offs, bodies)]
+        for v, b in zip(views, bodies):
+            v.copy_(b)
+        return views, packed, o
+
     # ---- re-parenting a variant (DESIGN §3.12) ------------------------------------------------------------------------------------
     @staticmethod
-    def _node_key(ref):
-        """What two walks compare: a plain tensor by its memory, an entry that holds its tensor plainly by that tensor, any other entry by itself."""
-        if ref[0] == "entry" and ref[2].raw is not None and ref[2].delta is False:
-            ref = ("tensor", ref[2].raw)
-        if ref[0] == "tensor":
-            return ("t", ref[1].data_ptr(), ref[1].numel() * ref[1].element_size())
-        return ("e", id(ref[2]))
-
-    @classmethod
-    def _patch_path(cls, ref):
-        """Walk base links from `ref` while the entry is "sparse" or "same" -> [(node key, the patches on the way there)]: the first element is `ref` itself with
-        no patch, the last the first node that is neither (a plain tensor, or an entry with a body of its own)."""
-        path, patches = [(cls._node_key(ref), ())], []
-        while ref[0] == "entry" and ref[2].delta in ("sparse", "same"):
-            e = ref[2]
-            if e.delta == "sparse":
-                patches.append(e.patch)
-            ref = e.base
-            path.append((cls._node_key(ref), tuple(patches)))
+    def _patch_path(ref):
+        """Walk base links from `ref` (a _BaseRef) while the entry is "sparse" or "same" -> [(node key, the patches on the way there)]: the first element is
+        `ref` itself with no patch, the last the first node that is neither (a plain tensor, or an entry with a body of its own)."""
+        path, patches = [(ref.key, ())], []
+        while ref.entry is not None and ref.entry.delta in ("sparse", "same"):
+            if ref.entry.delta == "sparse":
+                patches.append(ref.entry.patch)
+            ref = ref.entry.base
+            path.append((ref.key, tuple(patches)))
         return path
+
+    def _patch_lists(self, onto, refs):
+        """rebased, per tensor: where the walks from this store's entry and from onto's meet -> ({name: [the patches on both paths: their merge is the tensor's
+        patch over `onto`]}, [the names without such a list]).  refs: _base_items(onto)."""
+        lists, fallback = {}, []
+        for name, e in self._entries.items():
+            ref = refs.get(name)
+            ok = (ref is not None and ref.fits(e.dtype, e.shape) and e.P in (1, 2, 4) and e.P == _itemsize(e.dtype) and 0 < e.nbytes and e.nbytes // e.P < (1 << 32)
+                  and (ref.entry is None or ref.decodes_under((e.P, e.bits, e.byts, e.chunk))))      # (a resident base: what a "same" or sparse entry can decode over)
+            found = None
+            if ok:
+                mine, theirs = self._patch_path(_BaseRef(store=self, entry=e)), self._patch_path(_BaseRef(store=onto, entry=onto._entries[name]))
+                at = {k: ps for k, ps in reversed(theirs)}      # (the nearest occurrence of a key wins)
+                for k, ps in mine:
+                    if k in at:
+                        found = list(ps) + list(at[k])
+                        break
+            if found is None:
+                fallback.append(name)
+            else:
+                lists[name] = found
+        return lists, fallback
 
     def rebased(self, onto):
         """The same tensors as a NEW variant store whose base is `onto` — a ResidentCheckpoint on this store's device — without decoding what is kept as
@@ -621,26 +662,7 @@ class ResidentCheckpoint:
             raise ValueError(f"rebased: onto is a store on {self.device}, not on {onto.device}")
         dev, lib = self.device, _capi.lib()
         refs = self._base_items(onto, dev)
-        lists, fallback, entries = {}, [], {}
-        for name, e in self._entries.items():
-            ref = refs.get(name)
-            rb = None if ref is None else ref[1] if ref[0] == "tensor" else ref[2]
-            ok = (rb is not None and rb.dtype == e.dtype and tuple(rb.shape) == e.shape and e.P in (1, 2, 4) and e.P == torch.empty(0, dtype=e.dtype).element_size()
-                  and 0 < e.nbytes and e.nbytes // e.P < (1 << 32))
-            if ok and ref[0] == "entry":           # (what a "same" or sparse entry can decode over: from_state_dict's delta_ok)
-                ok = rb.decoded and (rb.P, rb.bits, rb.byts, rb.chunk) == (e.P, e.bits, e.byts, e.chunk)
-            found = None
-            if ok:
-                mine, theirs = self._patch_path(("entry", self, e)), self._patch_path(("entry", onto, onto._entries[name]))
-                at = {k: ps for k, ps in reversed(theirs)}      # (the nearest occurrence of a key wins)
-                for k, ps in mine:
-                    if k in at:
-                        found = list(ps) + list(at[k])
-                        break
-            if found is None:
-                fallback.append(name)
-            else:
-                lists[name] = found
+        lists, fallback = self._patch_lists(onto, refs)
         # rounds of pairwise merges, every tensor's in one call: a chain of depth d is d - 1 calls for the whole store
         scratch = []                               # the rounds' arenas: intermediate patches are views of them
         with _device_of(dev):
@@ -650,47 +672,29 @@ class ResidentCheckpoint:
                 scratch.append(got)
                 for n, g in zip(todo, got):
                     lists[n] = ([g] if g is not None else []) + lists[n][2:]
-        kept = []
+        merged = {}                                # {name: its one patch over `onto`, or None: the bytes are onto's}
         for name, ps in lists.items():
             if ps and ps[0].numel() >= self._entries[name].nbytes:
                 fallback.append(name)              # a patch that is not smaller than the tensor: the build decides what it is kept as
             else:
-                kept.append((name, ps[0] if ps else None))
-        offs, o = {}, 0
-        for name, p in kept:
-            if p is not None:
-                offs[name] = o
-                o += _round_up(p.numel())
-        packed = torch.empty(max(o, 1), dtype=torch.uint8, device=dev)
-        for name, p in kept:
+                merged[name] = ps[0] if ps else None
+        patched = [name for name, p in merged.items() if p is not None]
+        views, packed, o = self._pack([merged[name] for name in patched], dev)
+        mine, entries = dict(zip(patched, views)), {}
+        for name in merged:
             e, ref = self._entries[name], refs[name]
             prm = (e.P, e.bits, e.byts, e.chunk)
-            if p is None:
-                ne = _Entry(name, e.dtype, e.shape, e.nbytes, raw=ref[1] if ref[0] == "tensor" else None, params=prm)
-                ne.delta = "same"
+            if name in mine:
+                ne = _Entry.sparse(name, e.dtype, e.shape, ref, prm, mine[name], head=e.head)
             else:
-                ne = _Entry(name, e.dtype, e.shape, e.nbytes, params=prm)
-                ne.patch = packed[offs[name]:offs[name] + p.numel()]
-                ne.patch.copy_(p)
-                ne.delta, ne.entries = "sparse", _patch_entries(e.nbytes, e.P, p.numel())
-            ne.base = ne.restore = ref
-            ne.head = e.head
+                ne = _Entry.same(name, e.dtype, e.shape, ref, prm, head=e.head)
+            ne.restore = ref
             entries[name] = ne
         del scratch, lists
         keep, held = [packed], o
         order = {n: i for i, n in enumerate(self._entries)}
         fallback.sort(key=order.__getitem__)
-        groups, cur, size = [], [], 0
-        for name in fallback:
-            nb = self._entries[name].nbytes
-            if cur and size + nb > self._BUILD_GROUP_BYTES:
-                groups.append(cur)
-                cur, size = [], 0
-            cur.append(name)
-            size += nb
-        if cur:
-            groups.append(cur)
-        for grp in groups:
+        for grp in _groups(fallback, lambda name: self._entries[name].nbytes, self._BUILD_GROUP_BYTES):
             sub = type(self).from_state_dict(self.get_tensors(grp), dev, base=onto, sparse=True)
             entries.update(sub._entries)
             keep += [k for k in sub._keep if k is not onto]
@@ -732,10 +736,7 @@ class ResidentCheckpoint:
             def kind(e):                           # (None: the entry points without a kind, as ever)
                 return _capi.HINT_DELTA if e.delta is True else None
             sizes = [lib.hint_size_dev(e.window(0, e.chunks, None), stream, kind(e)) for e in todo]
-            offs, o = [], 0
-            for n in sizes:
-                offs.append(o)
-                o += _round_up(n)
+            offs, o = _packed(sizes)
             buf = torch.empty(max(o, 1), dtype=torch.uint8, device=self.device)
             for e, n, off in zip(todo, sizes, offs):
                 lib.hint_build_dev(e.window(0, e.chunks, None), buf.data_ptr() + off, n, stream, kind(e))
@@ -775,26 +776,18 @@ class ResidentCheckpoint:
             if e.delta is False:
                 plain.append((e, lo, hi, dst))
                 continue
+            bt = e.base.flat()                         # over a plain base tensor: read where it lies; over a resident base: its own sets decode the window first
+            if bt is not None:
+                keep.append(bt)
+            else:
+                via.setdefault(id(e.base.store), (e.base.store, []))[1].append((e.base.entry, lo, hi, dst))
             if e.delta == "sparse":
                 keep.append(e.patch)
-                if e.base[0] == "tensor":
-                    bt = codec.flat_bytes(e.base[1])
-                    keep.append(bt)
-                    patch.append(e.patch_item(lo, hi, ptr(dst), bt.data_ptr()))
-                else:
-                    _, bstore, be = e.base
-                    via.setdefault(id(bstore), (bstore, []))[1].append((be, lo, hi, dst))
-                    patch.append(e.patch_item(lo, hi, ptr(dst)))
-                continue
-            if e.base[0] == "tensor":                  # (a delta entry: "same" over a plain tensor is that tensor, never work)
-                bt = codec.flat_bytes(e.base[1])
-                keep.append(bt)
+                patch.append(e.patch_item(lo, hi, ptr(dst), bt.data_ptr() if bt is not None else None))
+            elif bt is not None:                       # (a delta entry: "same" over a plain tensor is that tensor, never work)
                 delta.append((e, lo, hi, ptr(dst), bt.data_ptr()))
-            else:
-                _, bstore, be = e.base
-                via.setdefault(id(bstore), (bstore, []))[1].append((be, lo, hi, dst))
-                if e.delta is True:
-                    delta.append((e, lo, hi, ptr(dst), ptr(dst) - lo * e.chunk))
+            elif e.delta is True:
+                delta.append((e, lo, hi, ptr(dst), ptr(dst) - lo * e.chunk))
         sets = []
         for bstore, w in via.values():
             sets += bstore._launch_sets(w, keep)
@@ -827,20 +820,7 @@ class ResidentCheckpoint:
         (zn_decode_status_chain), so that status() speaks for all of them."""
         lib = _capi.lib()
         with _device_of(self.device):
-            stream = _stream_of(self.device)
-            try:
-                for i, (kind, items) in enumerate(sets):
-                    if i == 1 and not check:
-                        lib.decode_status_chain(True)
-                    if kind == "hinted":
-                        lib.decompress_hinted_batch_dev(items, stream, check)
-                    elif kind == "patch":
-                        lib.patch_apply_batch_dev(items, stream, check)
-                    else:
-                        lib.decompress_window_batch_dev(items, stream, check)
-            finally:
-                if len(sets) > 1 and not check:
-                    lib.decode_status_chain(False)
+            _launch(lib, [(getattr(lib, _KINDS[kind][0]), items, None) for kind, items in sets], _stream_of(self.device), check)
 
     def _decode(self, work, check):
         """work: [(entry, chunk_lo, chunk_hi, flat uint8 destination)] -> batched decodes on the current stream, hinted where an entry has an index; one
@@ -880,9 +860,7 @@ class ResidentCheckpoint:
         """-> the frame header save_file writes in front of e's body: the torch-format header (with the shape extension) of a plain body — what
         compress_safetensors_file writes —, the BYTE-format header with the delta flag (byte 9 = 1, no shape extension) of a delta body: the form the
         reference's delta decode takes.  Bytes 0-15 are the entry's own (version, method, reorder modes, chunk exponent, dtype code)."""
-        head = e.head
-        if head is None:
-            head = ZipNN(input_format="torch", bytearray_dtype=e.dtype, method=COMPRESSION_METHOD).torch_frame_plan(torch.empty(e.shape, dtype=e.dtype, device="meta"))[0][:16]
+        head = e.head if e.head is not None else _frame_params_for(e.dtype, e.shape)[0]
         h = bytearray(HEADER_LEN)
         h[:16] = head
         h[8], h[9] = (EnumFormat.BYTE.value, 1) if e.delta is True else (EnumFormat.TORCH.value, 0)
@@ -910,8 +888,6 @@ class ResidentCheckpoint:
         zero bytes around it, so that a loaded patch is a 16-byte aligned view of the uploaded data section.  safetensors decides where an entry lies: the file
         is written with zero-filled entries under a temporary name, the patches are put at their places, and the file is renamed to `path`.  A patch whose
         L + 15 bytes would not be smaller than the tensor is written as the tensor (one decode).  A store without sparse entries writes the same file either way."""
-        import os
-        from safetensors.torch import save_file as st_save_file
         from . import safetensors_io
         lib = _capi.lib()
         patched = [e.name for e in self._entries.values() if e.patch is not None]
@@ -972,25 +948,7 @@ class ResidentCheckpoint:
             safetensors_io._set_digests_metadata(metadata, order, [recorded[n] for n in order])
         if kinds:
             safetensors_io._set_delta_metadata(metadata, kinds, self._ref_digests(refs, self.device))
-        if not patches:
-            st_save_file(tensors, path, metadata)
-            return path
-        tmp = f"{path}.tmp{os.getpid()}"
-        try:
-            st_save_file(tensors, tmp, metadata)
-            _, layout, data_start = safetensors_io._read_layout(tmp)
-            with open(tmp, "r+b") as f:
-                for name, mv in patches.items():
-                    lo, hi = layout[name][2], layout[name][3]
-                    at = (lo + 15) // 16 * 16                      # (of the DATA SECTION: what a reader uploads to an aligned allocation)
-                    assert hi - lo == len(mv) + safetensors_io.SPARSE_SLACK and at + len(mv) <= hi
-                    f.seek(data_start + at)
-                    f.write(mv)
-            os.replace(tmp, path)
-        finally:
-            if os.path.exists(tmp):
-                os.remove(tmp)
-        return path
+        return safetensors_io._save_with_sparse_entries(tensors, path, metadata, patches)
 
     # ---- decoding -------------------------------------------------------------------------------------------------------------
     def scratch_bytes(self, names):
@@ -998,13 +956,9 @@ class ResidentCheckpoint:
         return self._layout(names)[1]
 
     def _layout(self, names):
-        offs, o = {}, 0
-        for name in names:
-            e = self._entries[name]
-            if e.decoded and name not in offs:
-                offs[name] = o
-                o += _round_up(e.nbytes)
-        return offs, o
+        names = [name for name in dict.fromkeys(names) if self._entries[name].decoded]
+        offs, total = _packed(self._entries[name].nbytes for name in names)
+        return dict(zip(names, offs)), total
 
     def _destinations(self, names, into):
         """-> ({name: tensor view}, [(entry, flat uint8 destination)]) — compressed tensors inside `into` (allocated when None), others as they are."""
@@ -1093,18 +1047,11 @@ class ResidentCheckpoint:
                 codec.digest_device_batch(lib, [codec.flat_bytes(e.raw) if e.raw is not None else nothing for e in plain], stream, out=out[:len(plain)])
             if todo:
                 scratch = torch.empty(max(_round_up(e.nbytes) for e in todo), dtype=torch.uint8, device=self.device)
-                groups, cur, o = [], [], 0
-                for e in todo:
-                    if cur and o + _round_up(e.nbytes) > scratch.numel():
-                        groups.append(cur)
-                        cur, o = [], 0
-                    cur.append((e, scratch[o:o + e.nbytes]))
-                    o += _round_up(e.nbytes)
-                groups.append(cur)
                 k = len(plain)
-                for grp in groups:
-                    self._decode([(e, 0, e.chunks, flat) for e, flat in grp], False)
-                    codec.digest_device_batch(lib, [flat for _, flat in grp], stream, out=out[k:k + len(grp)])
+                for grp in _groups(todo, lambda e: _round_up(e.nbytes), scratch.numel()):
+                    flats = [scratch[o:o + e.nbytes] for e, o in zip(grp, _packed(e.nbytes for e in grp)[0])]
+                    self._decode([(e, 0, e.chunks, flat) for e, flat in zip(grp, flats)], False)
+                    codec.digest_device_batch(lib, flats, stream, out=out[k:k + len(grp)])
                     k += len(grp)
             vals = codec.digests_to_ints(out[:len(names)])
         return dict(zip([e.name for e in plain + todo], vals))
@@ -1124,11 +1071,7 @@ class ResidentCheckpoint:
 
     def _live_digests(self, pairs):
         """[(key, tensor)] -> {key: digest of the live tensor's bytes}: one batched launch, one read-back."""
-        if not pairs:
-            return {}
-        with _device_of(self.device):
-            vals = codec.digests_to_ints(codec.digest_device_batch(_capi.lib(), [codec.flat_bytes(t) for _, t in pairs], _stream_of(self.device)))
-        return {k: v for (k, _), v in zip(pairs, vals)}
+        return dict(zip([k for k, _ in pairs], codec.digests_of(_capi.lib(), [t for _, t in pairs], _stream_of(self.device))))
 
     def holds(self, target):
         """Do live tensors hold this store's values?  target: a module (named parameters and buffers) or a mapping of names to contiguous tensors on the
@@ -1149,13 +1092,12 @@ class ResidentCheckpoint:
                 want[e.name] = self._digests[e.name]
             elif e.restore is None:
                 continue                           # (the base has no such tensor: apply_ overwrites whatever is there)
-            elif e.restore[0] == "tensor":
-                pairs.append((("base", e.name), e.restore[1]))
+            elif e.restore.tensor is not None:
+                pairs.append((("base", e.name), e.restore.tensor))
+            elif e.restore.store._digests is None:
+                raise ValueError(f"guard: the base store has no digests (build it with digests=True) — {e.name}")
             else:
-                bstore, be = e.restore[1], e.restore[2]
-                if bstore._digests is None:
-                    raise ValueError(f"guard: the base store has no digests (build it with digests=True) — {e.name}")
-                want[e.name] = bstore._digests[be.name]
+                want[e.name] = e.restore.store._digests[e.restore.entry.name]
         got = self._live_digests(pairs)
         for (kind, name), _ in pairs:
             if kind == "base":
@@ -1167,13 +1109,8 @@ class ResidentCheckpoint:
     # ---- a variant applied to live weights ------------------------------------------------------------------------------------
     def _targets(self, target):
         """target: a module (named parameters and buffers) or a mapping -> [(entry, tensor)] for the names the store has."""
-        if isinstance(target, torch.nn.Module):
-            items = dict(target.named_parameters())
-            items.update(dict(target.named_buffers()))
-        else:
-            items = dict(target)
         out = []
-        for name, t in items.items():
+        for name, t in _named_tensors(target).items():
             e = self._entries.get(name)
             if e is None:
                 continue
@@ -1182,6 +1119,23 @@ class ResidentCheckpoint:
                 raise ValueError(f"{name}: a contiguous {e.dtype} tensor of shape {list(e.shape)} on {self.device}")
             out.append((e, t))
         return out
+
+    def _in_place_sets(self, target):
+        """What apply_ and revert_ share: the target's tensors that differ from the base's ("same" and empty entries do not) -> (the launch sets that XOR delta
+        bodies and patches into them IN PLACE — the same call both ways —, [(entry, tensor)] of the others: entries with a body or a tensor of their own, the
+        names of all of them)."""
+        inplace, patch, rest, names = [], [], [], []
+        for e, t in self._targets(target):
+            if e.delta == "same" or not e.nbytes:
+                continue
+            if e.delta is True:
+                inplace.append((e, 0, e.chunks, t.data_ptr(), t.data_ptr()))
+            elif e.delta == "sparse":
+                patch.append(e.patch_item(0, e.chunks, t.data_ptr()))
+            else:
+                rest.append((e, t))
+            names.append(e.name)
+        return self._delta_sets(inplace) + ([("patch", patch)] if patch else []), rest, names
 
     def apply_(self, target, check=True, guard=False):
         """Turn live BASE weights into the fine-tune's, in place: `target` is a module or a mapping of names to contiguous tensors on the store's device that
@@ -1193,21 +1147,14 @@ class ResidentCheckpoint:
         the very tensors this store holds as its plain base, the store decodes wrong values until revert_.  -> the names changed."""
         if guard:
             self._guard(target, True)
-        work, inplace, done, patch = [], [], [], []
-        for e, t in self._targets(target):
-            if e.delta == "same" or not e.nbytes:
-                continue
-            if e.delta is True:
-                inplace.append((e, 0, e.chunks, t.data_ptr(), t.data_ptr()))
-            elif e.delta == "sparse":
-                patch.append(e.patch_item(0, e.chunks, t.data_ptr()))
-            elif e.compressed:
+        sets, rest, done = self._in_place_sets(target)
+        work = []
+        for e, t in rest:
+            if e.compressed:
                 work.append((e, 0, e.chunks, codec.flat_bytes(t)))
             else:
                 t.copy_(e.raw)
-            done.append(e.name)
-        sets = self._launch_sets(work) + self._delta_sets(inplace) + ([("patch", patch)] if patch else [])
-        self._run_sets(sets, check)
+        self._run_sets(self._launch_sets(work) + sets, check)
         return done
 
     def revert_(self, target, check=True, guard=False):
@@ -1217,29 +1164,20 @@ class ResidentCheckpoint:
         guard=True (a store with digests): the live tensors must hold THIS store's values, else DigestMismatch is raised before anything is touched."""
         if guard:
             self._guard(target, False)
-        work, inplace, stay, via, patch = [], [], [], {}, []
-        for e, t in self._targets(target):
-            if e.delta == "same" or not e.nbytes:
-                continue
-            if e.delta is True:
-                inplace.append((e, 0, e.chunks, t.data_ptr(), t.data_ptr()))
-            elif e.delta == "sparse":
-                patch.append(e.patch_item(0, e.chunks, t.data_ptr()))
-            elif e.restore is None:
+        sets, rest, _ = self._in_place_sets(target)
+        stay, via = [], {}
+        for e, t in rest:
+            ref = e.restore
+            if ref is None or (ref.tensor is not None and ref.tensor.data_ptr() == t.data_ptr()):      # (nothing to restore from, or the base's tensor IS the target: its values are gone)
                 stay.append(e.name)
-            elif e.restore[0] == "tensor":
-                if e.restore[1].data_ptr() == t.data_ptr():          # (the base's tensor IS the target: its values are gone)
-                    stay.append(e.name)
-                else:
-                    t.copy_(e.restore[1])
+            elif ref.tensor is not None:
+                t.copy_(ref.tensor)
             else:
-                _, bstore, be = e.restore
-                via.setdefault(id(bstore), (bstore, []))[1].append((be, 0, be.chunks, codec.flat_bytes(t)))
-        sets = []
+                via.setdefault(id(ref.store), (ref.store, []))[1].append((ref.entry, 0, ref.entry.chunks, codec.flat_bytes(t)))
+        base_sets = []
         for bstore, w in via.values():
-            sets += bstore._launch_sets(w)
-        sets += self._delta_sets(inplace) + ([("patch", patch)] if patch else [])
-        self._run_sets(sets, check)
+            base_sets += bstore._launch_sets(w)
+        self._run_sets(base_sets + sets, check)
         return stay
 
     # ---- model integration ----------------------------------------------------------------------------------------------------
@@ -1305,13 +1243,11 @@ class ResidentPlan:
         with _device_of(store.device):
             # (a plain store: one zn_plan, as ever; a variant over a resident base: the base's plan, then the plan of the delta windows that run in place over
             #  what it decoded — run() launches them back to back on one stream)
-            hs = []
+            hs = []                                # per launch set: (the plan's run call, its handle, its destroy call)
             try:
                 for kind, items in (sets or [("window", [])]):
-                    if kind == "patch":
-                        hs.append((True, self._lib.patch_plan_create(items)))
-                    else:
-                        hs.append((False, self._lib.plan_create_hinted(items) if kind == "hinted" else self._lib.plan_create(items)))
+                    _, create, run, destroy = _KINDS[kind]
+                    hs.append((getattr(self._lib, run), getattr(self._lib, create)(items), getattr(self._lib, destroy)))
             except Exception:
                 self._destroy(hs)
                 raise
@@ -1322,29 +1258,17 @@ class ResidentPlan:
             raise RuntimeError("the plan is closed")
         self._stream = _stream_of(self._store.device, stream)
         with _device_of(self._store.device):
-            try:
-                for i, (is_patch, h) in enumerate(self._hs):
-                    if i == 1:
-                        self._lib.decode_status_chain(True)       # (the later plans add their verdict to the first one's: status() speaks for the whole run)
-                    if is_patch:
-                        self._lib.patch_plan_run(h, self._stream, False)
-                    else:
-                        self._lib.plan_run(h, self._stream, False)
-            finally:
-                if len(self._hs) > 1:
-                    self._lib.decode_status_chain(False)
+            _launch(self._lib, self._hs, self._stream, False)      # (the later plans add their verdict to the first one's: status() speaks for the whole run)
         return self.tensors
 
     def status(self):
         with _device_of(self._store.device):
             self._lib.decode_status(self._stream if self._stream is not None else _stream_of(self._store.device))
 
-    def _destroy(self, hs):
-        for is_patch, h in hs:
-            if is_patch:
-                self._lib.patch_plan_destroy(h)
-            else:
-                self._lib.plan_destroy(h)
+    @staticmethod
+    def _destroy(hs):
+        for _, h, destroy in hs:
+            destroy(h)
 
     def close(self):
         if self._hs is not None:

@@ -70,6 +70,27 @@ def file_delta(metadata):
     return kinds, base
 
 
+def _delta_over_base(filename, metadata, kinds, based):
+    """The tensors a delta file codes over its base, checked against that base before anything is uploaded.  kinds: file_delta's; based: {name: what the base
+    holds under that name, with .dtype, .shape and .fits(dtype, shape)} -> {name: (dtype, shape, based[name])}, the dtype and shape as `znn_compressed_vectors`
+    gives them.  A ValueError names the tensor that is listed but not compressed, has an unknown dtype, or that the base lacks or holds with another dtype or shape."""
+    import json
+    infos, over = get_compressed_tensors_metadata(metadata), {}
+    for name in kinds:
+        if name not in infos:
+            raise ValueError(f"{filename}: {name!r} is listed under znn_delta but not under znn_compressed_vectors")
+        dt, shape = getattr(torch, str(infos[name].get("dtype")), None), tuple(int(d) for d in json.loads(infos[name].get("shape", "[]")))
+        if not isinstance(dt, torch.dtype):
+            raise ValueError(f"{filename}: {name!r}: unknown dtype {infos[name].get('dtype')!r}")
+        ref = based.get(name)
+        if ref is None:
+            raise ValueError(f"{filename}: the base has no tensor {name!r}, which the file codes over it")
+        if not ref.fits(dt, shape):
+            raise ValueError(f"{filename}: {name!r} is {dt} {list(shape)} over a base tensor of the same dtype and shape; the base holds {ref.dtype} {list(ref.shape)}")
+        over[name] = (dt, shape, ref)
+    return over
+
+
 def _set_delta_metadata(metadata, kinds, base_digests):
     import json
     from . import codec
@@ -80,6 +101,74 @@ def _set_delta_metadata(metadata, kinds, base_digests):
 
 def _needs_base(filename):
     return ValueError(f"{filename}: a delta file ({DELTA_KEY}): its tensors are coded over a base — load it with load_file(base=) / ResidentCheckpoint.from_file(base=)")
+
+
+def _sparse_patch_at(lo):
+    """-> where the patch of a "sparse" entry that starts at `lo` lies: the entry's first multiple of 16 — offsets of the DATA SECTION, which a reader uploads
+    to an aligned allocation — with zero bytes around it, SPARSE_SLACK in all."""
+    return (lo + 15) // 16 * 16
+
+
+def _save_with_sparse_entries(tensors, path, metadata, patches):
+    """safetensors' save_file, then the "sparse" entries filled in -> path.  patches: {name: the patch's bytes}; tensors[name] is that entry zero-filled
+    (len(patch) + SPARSE_SLACK bytes).  safetensors decides where an entry lies: the file is written under a temporary name, the patches are put at their places
+    (_sparse_patch_at), and the file is renamed to `path`."""
+    from safetensors.torch import save_file as st_save_file
+    if not patches:
+        st_save_file(tensors, path, metadata)
+        return path
+    tmp = f"{path}.tmp{os.getpid()}"
+    try:
+        st_save_file(tensors, tmp, metadata)
+        _, layout, data_start = _read_layout(tmp)
+        with open(tmp, "r+b") as f:
+            for name, mv in patches.items():
+                lo, hi = layout[name][2], layout[name][3]
+                at = _sparse_patch_at(lo)
+                assert hi - lo == len(mv) + SPARSE_SLACK and at + len(mv) <= hi
+                f.seek(data_start + at)
+                f.write(mv)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return path
+
+
+def _read_sparse_entries(filename, lay, over, check_slack):
+    """The "sparse" entries of a delta file, from the file alone, before anything is uploaded.  lay: _read_layout(filename); over: {name: (dtype, shape)} ->
+    {name: (offset of the patch in the data section, L, elem)}.  The patch starts at _sparse_patch_at of its entry; its header must describe the tensor and give
+    the entry's length; check_slack: the up to 15 bytes of the entry around the patch must be zero.  A ValueError names the tensor."""
+    if not over:
+        return {}
+    import math
+    from . import _capi
+    _, layout, data_start = lay
+    lib, out = _capi.lib(), {}
+    with open(filename, "rb") as f:
+        for name, (dt, shape) in over.items():
+            fdt, _, lo, hi = layout[name]
+            elem = torch.empty(0, dtype=dt).element_size()
+            n = elem * math.prod(int(d) for d in shape)
+            at = _sparse_patch_at(lo)
+            if fdt != torch.uint8 or hi - lo < 32 + SPARSE_SLACK:
+                raise ValueError(f"{filename}: {name!r} is listed as \"sparse\" but its entry of {hi - lo} bytes cannot hold a patch")
+            f.seek(data_start + lo)
+            slack = f.read(at - lo)
+            head = f.read(32)
+            T, L = int.from_bytes(head[16:24], "little"), int.from_bytes(head[24:32], "little")
+            if head[:4] != b"ZNP1" or head[4] != elem or int.from_bytes(head[8:16], "little") != n:
+                raise ValueError(f"{filename}: {name!r}: the patch's header does not describe a {dt} tensor of {n} bytes")
+            if hi - lo != L + SPARSE_SLACK:
+                raise ValueError(f"{filename}: {name!r}: an entry of {hi - lo} bytes for a patch of {L} (the entry is the patch and {SPARSE_SLACK} bytes)")
+            if T > n // elem or lib.patch_len(n, elem, T) != L:
+                raise ValueError(f"{filename}: {name!r}: {L} bytes is not the length of a patch of {T} elements")
+            if check_slack:
+                f.seek(data_start + at + L)
+                if any(slack) or any(f.read(hi - at - L)):
+                    raise ValueError(f"{filename}: {name!r}: the bytes around the patch are not zero")
+            out[name] = (at, L, elem)
+    return out
 
 
 def _set_digests_metadata(metadata, names, values):
@@ -387,10 +476,11 @@ class _Uploaded:
         self.heads = heads or {}          # per compressed tensor: the first 16 bytes of its frame header (magic … dtype code)
 
 
-def _upload_file(filename, device, delta=False):
+def _upload_file(filename, device, delta=False, lay=None):
     """First half of decode_file_on_device, and how resident.ResidentCheckpoint.from_file gets its frames into HBM: every frame header parsed
     from the host mapping, then the file's data section to the device in ONE transfer.  -> _Uploaded, or None when the container names a dtype
-    this parser does not know.  A delta file (znn_delta) is refused unless the caller says it brings the base (delta=True): its "same" and "sparse" entries hold no frame."""
+    this parser does not know.  A delta file (znn_delta) is refused unless the caller says it brings the base (delta=True): its "same" and "sparse" entries hold no frame.
+    lay: what _read_layout(filename) gave, where the caller has read it already."""
     import contextlib
     import mmap
     import threading
@@ -400,7 +490,7 @@ def _upload_file(filename, device, delta=False):
     dev = torch.device(device)
     while _PENDING_CLOSERS:                            # mappings of earlier calls, unmapped on helper threads (below)
         _PENDING_CLOSERS.pop().join()
-    lay = _read_layout(filename)
+    lay = lay if lay is not None else _read_layout(filename)
     if lay is None:
         return None
     lib = _capi.lib()
@@ -462,7 +552,7 @@ def _decode_uploaded(lib, codec, dev, layout, infos, plan, total, blob, use_aren
         packed = b"".join([pack(base_in + b0, hi - b0, (((base_out + off) if use_arena else outs[i].data_ptr()) if fp[5] else 0), fp[5],
                                 fp[1], fp[2], fp[3], fp[4], 0) for i, (_, b0, hi, fp, off) in enumerate(plan)])
         stream = codec._stream_handle(blob)
-        with torch.cuda.device(dev) if dev.type == "cuda" else codec._nullctx():
+        with codec._device_of(dev):
             lib.decompress_batch_dev_packed(packed, len(plan), stream, check=False)      # asynchronous: the verdict is asked for below
         ta_ = time.perf_counter()
         # (views while the kernels run: one typed view of the arena per dtype, one as_strided per tensor)
@@ -483,7 +573,7 @@ def _decode_uploaded(lib, codec, dev, layout, infos, plan, total, blob, use_aren
                 out[name] = outs[i].view(dt).reshape(shape) if shape is not None else outs[i].view(dt)
     tb_ = time.perf_counter()
     if plan:
-        with torch.cuda.device(dev) if dev.type == "cuda" else codec._nullctx():
+        with codec._device_of(dev):
             lib.decode_status(stream)                  # waits for the decode; raises for a corrupt frame exactly as a checked call would
     tc_ = time.perf_counter()
     if not compressed_only:
