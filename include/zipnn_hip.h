@@ -394,6 +394,43 @@ typedef struct zn_patch_merge_item {
 int zn_patch_merge_size_batch_dev(const zn_patch_merge_item* items, size_t count, size_t* sizes_out, void* stream);
 int zn_patch_merge_batch_dev(zn_patch_merge_item* items, size_t count, void* stream);
 
+/* SHARDING PATCHES.  A patch is a sorted list of element indices, so the patch of a rectangle of a tensor follows from the tensor's patch without the tensor.
+ * View the tensor as rows x cols elements and take rows [row_lo, row_hi) and cols [col_lo, col_hi), h x w elements.  The map from the rectangle's row-major index
+ * j to the tensor's, phi(j) = (row_lo + j / w) cols + col_lo + j % w, is strictly increasing: SELECT keeps the entries inside the rectangle and re-indexes them
+ * by the inverse of phi, PLACE re-indexes a rectangle's entries by phi; both re-block into blocks of 65 536 elements, neither sorts.  The format is canonical, so
+ *   select(patch(T over B))           is byte for byte  patch(T[rect] over B[rect]),
+ *   place(patch(S over B[rect]))      is byte for byte  patch(B with its rectangle set to S, over B),
+ *   select(place(p)) == p, and the XOR-merge (above) of the placed selects of rectangles that tile the tensor is the tensor's patch again.
+ * A narrow(dim, lo, hi - lo) of any shape is such a rectangle: rows = prod(shape[:dim]), cols = shape[dim] inner, cols [lo inner, hi inner), all rows.
+ * zn_patch_select_size_batch_dev / zn_patch_place_size_batch_dev: the count pass alone — sizes_out[i] = L of item i's result, or 0 when no entry results; one
+ *   read-back; d_out / out_cap ignored.
+ * zn_patch_select_batch_dev / zn_patch_place_batch_dev: count, scan (zn_k_patch_scan), one read-back (totals and the verdict), emit; synchronous, like build and
+ *   merge.  out_len = L, or 0 (nothing written) when no entry results.  ZN_E_CAP when a capacity is short: every out_len then holds what is needed and nothing
+ *   was written.
+ * The input's header must carry n = rows cols elem for select and n = h w elem for place.  ZN_E_ARG before any launch: an empty rectangle or one that is not
+ * inside the tensor, an elem that is not 1, 2 or 4, rows cols >= 2^32, d_patch or d_out null or not 16-byte aligned, patch_len < 32, or [d_out, d_out + out_cap)
+ * overlapping the input.
+ * Inputs may come from anywhere.  The kernels read nothing outside [d_patch, d_patch + patch_len) — the header first: magic, E and n against the item, T <= m, L
+ * against patch_len and the formula's value for T — and, for every input block a workgroup visits, first[b] <= first[b + 1] <= T, first[0] == 0, first[NB] == T,
+ * no more entries than the block has elements, and for every entry of it: the index inside the tensor, offsets strictly ascending, no zero value.  What a returned
+ * ZN_OK has validated: PLACE — the whole input (every input block is visited); SELECT — the header and the input blocks it visits (for each output block: those from
+ * its first element's to its last element's, so at least every block that holds an element of the rectangle), and NOTHING of the others — blocks in front of the
+ * rectangle's first row, behind its last, or in the gap between two output blocks: validating the rest is zn_patch_check_batch_dev's job.  (The canonical
+ * padding is never looked at.)  Anything wrong in any visited part of any item is ZN_E_CORRUPT for the call: the outputs are then unspecified, and nothing outside
+ * [d_out, d_out + out_cap) was written. */
+typedef struct zn_patch_select_item {
+  const void* d_patch; size_t patch_len;    /* 16-byte aligned, len >= 32 */
+  int elem;
+  size_t rows, cols;                        /* the WHOLE tensor as rows x cols elements; rows * cols < 2^32 */
+  size_t row_lo, row_hi, col_lo, col_hi;    /* the rectangle, non-empty, inside the tensor */
+  void* d_out; size_t out_cap;              /* 16-byte aligned; does not overlap the input */
+  size_t out_len;                           /* out: L, or 0 (nothing written) when no entry results */
+} zn_patch_select_item;
+int zn_patch_select_size_batch_dev(const zn_patch_select_item* items, size_t count, size_t* sizes_out, void* stream);
+int zn_patch_select_batch_dev(zn_patch_select_item* items, size_t count, void* stream);
+int zn_patch_place_size_batch_dev(const zn_patch_select_item* items, size_t count, size_t* sizes_out, void* stream);
+int zn_patch_place_batch_dev(zn_patch_select_item* items, size_t count, void* stream);
+
 /* Plumbing for callers that keep the tensors in HBM but hold pageable host buffers (files, Python bytes): the same
  * pinned, multi-threaded transfer the host-buffer entry points above use internally (zipnn_amd/csrc/zn_host_pipe.hpp),
  * on the current device; returns when the n bytes have arrived.  No reference counterpart — the reference's buffers

@@ -43,6 +43,10 @@ blocks of leg b as the base, the two fine-tunes of --delta:
   r  a chain of four 2 % steps and two sibling fine-tunes over a resident indexed base, every comparison interleaved in both orders (A B A B B A B A: the four A
      runs are the A/A spread): rebased against get_tensors + from_state_dict; the merge call against the build call on the same pairs; plan.run of one block
      from the chain against the flattened store; sw.apply_ against a.revert_ + b.apply_; resident bytes of b over the base against b over a
+--shard: patch selects and ResidentCheckpoint.sharded instead, into profiles/resident_shard.{json,txt}:
+  h  one rank of a split of 8 of a 2 % fine-tune over a resident indexed base (q/k/v/gate/up along dim 0, o/down along dim 1), every comparison interleaved in
+     both orders (A B A B B A B A: the four A runs are the A/A spread): sharded against get_tensors + narrow + from_state_dict; the select call against the build
+     call on the same shard pairs, dim 0 and dim 1 apart; plan.run of one block from the sharded store against a store built from the shard tensors
 """
 import argparse
 import json
@@ -871,6 +875,132 @@ def main_rebase(args):
     return 0
 
 
+def leg_h(args):
+    """--shard: see the module docstring."""
+    import torch
+    from zipnn_amd import ResidentCheckpoint, _capi, codec
+    lib = _capi.lib()
+    sd, per = _blocks(args.layers)
+    names = per[0]
+    base = ResidentCheckpoint.from_state_dict(sd, "cuda:0", index=True)
+    ft_sd = _fine_tune(sd, "sparse", 41)
+    ft = ResidentCheckpoint.from_state_dict(ft_sd, "cuda:0", base=base, sparse=True)
+    ways, rank = 8, 1
+    spec = {}
+    for k, v in sd.items():
+        dim = 0 if any(p in k for p in ("q_proj", "k_proj", "v_proj", "gate_proj", "up_proj")) else 1 if any(p in k for p in ("o_proj", "down_proj")) else None
+        if dim is not None:
+            spec[k] = (dim, rank * v.shape[dim] // ways, (rank + 1) * v.shape[dim] // ways)
+
+    def cut(d):
+        return {k: (v.narrow(spec[k][0], spec[k][1], spec[k][2] - spec[k][1]).contiguous() if k in spec else v) for k, v in d.items()}
+    onto, want = cut(sd), cut(ft_sd)
+    order = ("A", "B", "A", "B", "B", "A", "B", "A")
+
+    def wall(fn):
+        torch.cuda.synchronize(); t0 = time.perf_counter(); r = fn(); torch.cuda.synchronize()
+        return r, (time.perf_counter() - t0) * 1e3
+
+    def abab(fa, fb, timer):
+        runs = {"A": [], "B": []}
+        for leg in order:
+            runs[leg].append(timer(fa if leg == "A" else fb))
+        a, b = runs["A"], runs["B"]
+        return {"A_ms": a, "B_ms": b, "aa_spread": (max(a) - min(a)) / min(a), "B_over_A": (sum(b) / len(b)) / (sum(a) / len(a))}
+
+    def route():                                   # what sharded replaces
+        got = ft.get_tensors(list(ft_sd))
+        return ResidentCheckpoint.from_state_dict({k: (got[k].narrow(spec[k][0], spec[k][1], spec[k][2] - spec[k][1]).contiguous() if k in spec else got[k]) for k in ft_sd},
+                                                  "cuda:0", base=onto, sparse=True)
+    mine, direct = ft.sharded(onto, spec), route()
+    for s, tag in ((mine, "sharded"), (direct, "route")):
+        got = s.get_tensors(list(ft_sd))
+        for k in ft_sd:
+            assert _same(got[k], want[k]), (tag, k)
+        del got
+    for k in ft_sd:
+        assert mine.info(k)["delta"] == direct.info(k)["delta"] and mine.info(k)["patch_entries"] == direct.info(k)["patch_entries"], k
+        if mine.info(k)["delta"] == "sparse":
+            assert torch.equal(mine._entries[k].patch, direct._entries[k].patch), k
+    res = {"layers": args.layers, "tensors": len(sd), "nbytes": base.nbytes, "ways": ways, "rank": rank, "shard_nbytes": mine.nbytes,
+           "ft_resident_bytes": ft.resident_bytes, "shard_resident_bytes": mine.resident_bytes,
+           "sparse_entries": sum(1 for k in ft_sd if mine.info(k)["delta"] == "sparse"), "patch_entries": sum(mine.info(k)["patch_entries"] or 0 for k in ft_sd)}
+    # 1. sharded (B) against the route it replaces (A), wall
+    res["shard_wall"] = abab(route, lambda: ft.sharded(onto, spec), lambda fn: wall(fn)[1])
+    ft.sharded(onto, spec)
+    res["shard_kernels"] = _capi_kernels()
+    # 2. the select call alone (B) against the build call on the same materialised shard pairs (A), dim 0 and dim 1 apart
+    st = torch.cuda.current_stream().cuda_stream
+    res["select_call"] = {}
+    for dim in (0, 1):
+        ks = [k for k in spec if spec[k][0] == dim and ft.info(k)["delta"] == "sparse"]
+        items = [(ft._entries[k].patch, 2) + codec.narrow_rect(sd[k].shape, *spec[k]) for k in ks]
+        args_ = [(it[0].data_ptr(), it[0].numel()) + tuple(it[1:]) for it in items]
+        sizes = lib.patch_select_size_batch_dev(args_, st)
+        pairs = [(codec.flat_bytes(want[k]), codec.flat_bytes(onto[k]), 2) for k in ks]
+        assert codec.patch_sizes_device_batch(lib, pairs) == sizes
+        offs, o = [], 0
+        for n in sizes:
+            offs.append(o); o += (n + 255) // 256 * 256
+        out_s, out_b = (torch.empty(max(o, 16), dtype=torch.uint8, device="cuda") for _ in range(2))
+        si = [a + (out_s.data_ptr() + off, cap) for a, off, cap in zip(args_, offs, sizes)]
+        bi = [(s.data_ptr(), b.data_ptr(), s.numel(), el, out_b.data_ptr() + off, cap) for (s, b, el), off, cap in zip(pairs, offs, sizes)]
+        assert lib.patch_select_batch_dev(si, st) == sizes and lib.patch_build_batch_dev(bi, st) == sizes
+        for off, n in zip(offs, sizes):
+            assert torch.equal(out_s[off:off + n], out_b[off:off + n]), "the select is not the build"
+        r = abab(lambda: lib.patch_build_batch_dev(bi, st), lambda: lib.patch_select_batch_dev(si, st), lambda fn: _events_ms(fn, args.reps)["median_ms"])
+        r.update({"items": len(ks), "input_bytes": sum(it[0].numel() for it in items), "output_bytes": sum(sizes), "shard_bytes": sum(want[k].numel() * 2 for k in ks)})
+        r["select_gb_per_s"] = (r["input_bytes"] + r["output_bytes"]) / (statistics.median(r["B_ms"]) * 1e-3) / 1e9
+        res["select_call"][str(dim)] = r
+        del out_s, out_b
+    # 3. plan.run of one block: a store built directly from the shard tensors (A) against the sharded store (B)
+    scratch = torch.empty(mine.scratch_bytes(names), dtype=torch.uint8, device="cuda")
+
+    def plan_ms(store):
+        plan = store.plan(names, into=scratch)
+        t = _events_ms(plan.run, args.reps)["median_ms"]
+        plan.status()
+        for k in names:
+            assert _same(plan.tensors[k], want[k]), k
+        plan.close()
+        return t
+    res["plan_run"] = abab(lambda: direct, lambda: mine, lambda pick: plan_ms(pick()))
+    return res
+
+
+def main_shard(args):
+    p = subprocess.run(["timeout", "-k", "10", "900", sys.executable, os.path.abspath(__file__), "--leg", "h", "--layers", str(args.layers), "--reps", str(args.reps)],
+                       capture_output=True, text=True)
+    line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+    if p.returncode != 0 or not line:
+        print(f"leg h failed (exit {p.returncode})\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}")
+        return p.returncode or 1
+    res = json.loads(line[0][7:])
+    out = args.out if args.out != os.path.join(ROOT, "profiles", "resident_decode") else os.path.join(ROOT, "profiles", "resident_shard")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+
+    def row(title, r, a, b):
+        return [f"  {title}", f"          {a} " + " / ".join(f"{x:.4f}" for x in r["A_ms"]) + f"   {b} " + " / ".join(f"{x:.4f}" for x in r["B_ms"]) +
+                f"   ms; {b} = {r['B_over_A']:.3f} of {a}  (A/A spread of the {a} runs: {100 * r['aa_spread']:.1f} %)"]
+    lines = [f"command: python scripts/bench_resident.py --shard --layers {args.layers} --reps {args.reps}",
+             "patch select probe (zn_patch_select_batch_dev, ResidentCheckpoint.sharded, DESIGN §3.13): a 2 % fine-tune, sparse, over a resident indexed base of",
+             f"{res['layers']} Llama-3-8B blocks (bf16, {res['tensors']} tensors, {res['nbytes']} B); rank {res['rank']} of a split of {res['ways']}: q/k/v/gate/up along dim 0, o/down along dim 1,",
+             "over the rank's shards of the base as plain tensors; every comparison interleaved in both orders (A B A B B A B A), every result checked against the narrowed tensors",
+             f"  the shard store: {res['shard_nbytes']} B of tensors, {res['sparse_entries']} sparse tensors, {res['patch_entries']} entries, {res['shard_resident_bytes']} B resident"
+             f" (the whole fine-tune: {res['ft_resident_bytes']} B)"]
+    lines += row("1. one rank's store, wall ms: get_tensors + narrow().contiguous() + from_state_dict(base=onto, sparse=True) against ft.sharded(onto, spec)", res["shard_wall"], "route", "sharded")
+    lines.append(f"          kernels of sharded's last call [{res['shard_kernels']}]")
+    for dim in ("0", "1"):
+        m = res["select_call"][dim]
+        lines += row(f"2. dim {dim}, the call alone, device events, median ms: zn_patch_build_batch_dev from the shard tensors ({m['shard_bytes']} B twice) against zn_patch_select_batch_dev on the"
+                     f" whole patches of the same {m['items']} tensors ({m['input_bytes']} B in, {m['output_bytes']} B out: {m['select_gb_per_s']:.1f} GB/s over both)", m, "build", "select")
+    lines += row("3. plan.run of one block, device events, median ms: a store built from the shard tensors against the sharded store (identical patches)", res["plan_run"], "built", "sharded")
+    open(out + ".txt", "w").write("\n".join(lines) + "\n")
+    json.dump(res, open(out + ".json", "w"), indent=1)
+    print("\n".join(lines))
+    return 0
+
+
 def main_sparse(args):
     p = subprocess.run(["timeout", "-k", "10", "540", sys.executable, os.path.abspath(__file__), "--leg", "s", "--layers", str(args.layers), "--reps", str(args.reps)],
                        capture_output=True, text=True)
@@ -1038,6 +1168,7 @@ def main():
     ap.add_argument("--sparse", action="store_true", help="the sparse variant leg (s) instead of a-e")
     ap.add_argument("--sparse-file", action="store_true", help="the sparse file leg (f) instead of a-e")
     ap.add_argument("--rebase", action="store_true", help="the patch merge / rebased leg (r) instead of a-e")
+    ap.add_argument("--shard", action="store_true", help="the patch select / sharded leg (h) instead of a-e")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resident_decode"))
     args = ap.parse_args()
     if args.leg:                                          # a child: one leg, its result as one JSON line
@@ -1059,6 +1190,8 @@ def main():
         return main_sparse_file(args)
     if args.rebase:
         return main_rebase(args)
+    if args.shard:
+        return main_shard(args)
     results = {}
     for leg, limit in LEG_SECONDS.items():
         p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--layers", str(args.layers), "--reps", str(args.reps)],

@@ -37,7 +37,9 @@ HOT = [("zn_k_decode_fusedILi1ELb0ELb0E", "decode_fused<1> plain"), ("zn_k_decod
        ("11zn_k_digest8", "digest (zn64-1, §3.8)"), ("16zn_k_digest_init", "digest_init"),
        ("zn_k_patch_count", "patch_count (znp1, §3.10)"), ("zn_k_patch_scan", "patch_scan"), ("zn_k_patch_emit", "patch_emit"), ("zn_k_patch_apply", "patch_apply"),
        ("zn_k_patch_check", "patch_check (§3.11)"),
-       ("zn_k_patch_merge_count", "patch_merge_count (§3.12)"), ("zn_k_patch_merge_emit", "patch_merge_emit")]
+       ("zn_k_patch_merge_count", "patch_merge_count (§3.12)"), ("zn_k_patch_merge_emit", "patch_merge_emit"),
+       ("zn_k_patch_select_count", "patch_select_count (§3.13)"), ("zn_k_patch_select_emit", "patch_select_emit"),
+       ("zn_k_patch_place_count", "patch_place_count"), ("zn_k_patch_place_emit", "patch_place_emit")]
 
 
 def kernels_of(obj):

@@ -6,10 +6,10 @@ repository's scope and raises NotImplementedError.
 """
 from .zipnn import ZipNN, SafeOpen, zipnn_safetensors, zipnn_hf, decompress_safetensors_tensor  # noqa: F401
 from .resident import ResidentCheckpoint  # noqa: F401
-from .codec import digest, digest_many, DigestMismatch, patch_build, patch_apply_, patch_check, patch_merge  # noqa: F401
+from .codec import digest, digest_many, DigestMismatch, patch_build, patch_apply_, patch_check, patch_merge, patch_select, patch_place  # noqa: F401
 
 __all__ = ["ZipNN", "SafeOpen", "zipnn_safetensors", "zipnn_hf", "decompress_safetensors_tensor", "ResidentCheckpoint", "digest", "digest_many", "DigestMismatch",
-           "patch_build", "patch_apply_", "patch_check", "patch_merge"]
+           "patch_build", "patch_apply_", "patch_check", "patch_merge", "patch_select", "patch_place"]
 
 
 def install_as_zipnn():

@@ -115,6 +115,16 @@ class ZnPatchMergeItem(ctypes.Structure):
 assert ctypes.sizeof(ZnPatchMergeItem) == 72
 
 
+class ZnPatchSelectItem(ctypes.Structure):
+    """struct zn_patch_select_item of include/zipnn_hip.h"""
+    _fields_ = [("d_patch", ctypes.c_void_p), ("patch_len", ctypes.c_size_t), ("elem", ctypes.c_int), ("rows", ctypes.c_size_t), ("cols", ctypes.c_size_t),
+                ("row_lo", ctypes.c_size_t), ("row_hi", ctypes.c_size_t), ("col_lo", ctypes.c_size_t), ("col_hi", ctypes.c_size_t),
+                ("d_out", ctypes.c_void_p), ("out_cap", ctypes.c_size_t), ("out_len", ctypes.c_size_t)]
+
+
+assert ctypes.sizeof(ZnPatchSelectItem) == 96
+
+
 # the bits of a zn_patch_check_batch_dev verdict
 PATCH_BAD_HEADER, PATCH_BAD_FIRST, PATCH_BAD_OFFSET, PATCH_BAD_VALUE, PATCH_BAD_PADDING = 1, 2, 4, 8, 16
 
@@ -239,6 +249,13 @@ class ZnLib:
             L.zn_patch_merge_size_batch_dev.argtypes = [ctypes.POINTER(ZnPatchMergeItem), sz, ctypes.POINTER(sz), vp]
             L.zn_patch_merge_batch_dev.restype = ci
             L.zn_patch_merge_batch_dev.argtypes = [ctypes.POINTER(ZnPatchMergeItem), sz, vp]
+        if hasattr(L, "zn_patch_select_batch_dev"):     # (likewise: a library from before select / place)
+            for f in (L.zn_patch_select_size_batch_dev, L.zn_patch_place_size_batch_dev):
+                f.restype = ci
+                f.argtypes = [ctypes.POINTER(ZnPatchSelectItem), sz, ctypes.POINTER(sz), vp]
+            for f in (L.zn_patch_select_batch_dev, L.zn_patch_place_batch_dev):
+                f.restype = ci
+                f.argtypes = [ctypes.POINTER(ZnPatchSelectItem), sz, vp]
         L.zn_copy_to_host.restype = ci; L.zn_copy_to_host.argtypes = [vp, vp, sz]
         L.zn_release_workspace.restype = ci
         L.zn_set_legacy_tree_descriptions.restype = ci
@@ -704,6 +721,46 @@ class ZnLib:
         arr, n = self._patch_merge_items(items)
         self._check(self._L.zn_patch_merge_batch_dev(arr, n, ctypes.c_void_p(stream or None)))
         return [int(arr[i].out_len) for i in range(n)]
+
+    @staticmethod
+    def _patch_select_items(items):
+        items = list(items)
+        arr = (ZnPatchSelectItem * max(len(items), 1))()
+        for i, it in enumerate(items):
+            a = arr[i]
+            pp, a.patch_len, a.elem, a.rows, a.cols, a.row_lo, a.row_hi, a.col_lo, a.col_hi = it[:9]
+            a.d_patch = pp or None
+            if len(it) > 9:
+                a.d_out = it[9] or None; a.out_cap = it[10]
+        return arr, len(items)
+
+    def _patch_select_sizes(self, fn, items, stream):
+        arr, n = self._patch_select_items(items)
+        out = (ctypes.c_size_t * max(n, 1))()
+        self._check(fn(arr, n, out, ctypes.c_void_p(stream or None)))
+        return [int(out[i]) for i in range(n)]
+
+    def _patch_select_run(self, fn, items, stream):
+        arr, n = self._patch_select_items(items)
+        self._check(fn(arr, n, ctypes.c_void_p(stream or None)))
+        return [int(arr[i].out_len) for i in range(n)]
+
+    def patch_select_size_batch_dev(self, items, stream=0):
+        """zn_patch_select_size_batch_dev.  items: iterable of (patch_ptr, patch_len, elem, rows, cols, row_lo, row_hi, col_lo, col_hi) -> the lengths of the
+        patches of those rectangles (0: no entry inside); the count pass only.  A malformed input is ZnError(ZN_E_CORRUPT)."""
+        return self._patch_select_sizes(self._L.zn_patch_select_size_batch_dev, items, stream)
+
+    def patch_select_batch_dev(self, items, stream=0):
+        """zn_patch_select_batch_dev.  items: as for the size call, then (out_ptr, out_cap) -> the results' lengths (0: no entry inside, nothing written)."""
+        return self._patch_select_run(self._L.zn_patch_select_batch_dev, items, stream)
+
+    def patch_place_size_batch_dev(self, items, stream=0):
+        """zn_patch_place_size_batch_dev: the inverse — the patch covers the rectangle, the result the whole tensor.  Items and result as for select."""
+        return self._patch_select_sizes(self._L.zn_patch_place_size_batch_dev, items, stream)
+
+    def patch_place_batch_dev(self, items, stream=0):
+        """zn_patch_place_batch_dev.  Items and result as for patch_select_batch_dev."""
+        return self._patch_select_run(self._L.zn_patch_place_batch_dev, items, stream)
 
     def decode_status(self, stream=0):
         """zn_decode_status: wait for `stream`, raise what the last check=False decode call on this device would have raised."""

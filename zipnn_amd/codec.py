@@ -400,6 +400,87 @@ def patch_merge(pa, pb):
     return patch_merge_device_batch(_capi.lib(), [(pa, pb, na, ea)])[0]
 
 
+def patch_select_device_batch(lib, items, place=False, sizes=None, return_arena=False):
+    """items: [(patch, elem, rows, cols, row_lo, row_hi, col_lo, col_hi)] on one device, the patches contiguous uint8 tensors at 16-byte aligned addresses ->
+    place=False: the patches of those rectangles of the tensors the inputs cover; place=True: the inputs cover the rectangles, the results the whole tensors
+    (include/zipnn_hip.h, SHARDING PATCHES).  uint8 tensors (views of one allocation, each at a multiple of 256 bytes), None where no entry results — by ONE
+    zn_patch_select_batch_dev / zn_patch_place_batch_dev call.  sizes: the lengths the size call gave for the same items (else they are counted here).
+    return_arena: (arena, offsets, lengths) instead."""
+    items = list(items)
+    if not items:
+        return (None, [], []) if return_arena else []
+    dev = items[0][0].device
+    for it in items:
+        p = it[0]
+        if p.dtype != torch.uint8 or p.device != dev or not p.is_contiguous():
+            raise ValueError("patch select: contiguous uint8 tensors on one device")
+    args = [(it[0].data_ptr(), it[0].numel()) + tuple(it[1:8]) for it in items]
+    with _device_of(dev):
+        if sizes is None:
+            sizes = (lib.patch_place_size_batch_dev if place else lib.patch_select_size_batch_dev)(args, _stream_handle(items[0][0]))
+        offs, o = [], 0
+        for n in sizes:
+            offs.append(o)
+            o += (n + 255) // 256 * 256
+        arena = torch.empty(max(o, 16), dtype=torch.uint8, device=dev)
+        lens = (lib.patch_place_batch_dev if place else lib.patch_select_batch_dev)(
+            [a + (arena.data_ptr() + off if cap else 0, cap) for a, off, cap in zip(args, offs, sizes)], _stream_handle(arena))
+    if return_arena:
+        return arena, offs, lens
+    return [arena[off:off + n] if n else None for off, n in zip(offs, lens)]
+
+
+def narrow_rect(shape, dim, lo, hi):
+    """A narrow(dim, lo, hi - lo) of a tensor of `shape` as a rectangle of its elements -> (rows, cols, row_lo, row_hi, col_lo, col_hi): rows = prod(shape[:dim]),
+    cols = shape[dim] * inner, all rows, cols [lo * inner, hi * inner).  ValueError for a dimension or a range the shape does not have."""
+    shape = tuple(int(s) for s in shape)
+    if not -len(shape) <= dim < len(shape):
+        raise ValueError(f"dimension {dim} of a tensor of shape {shape}")
+    dim %= len(shape)
+    if not 0 <= lo < hi <= shape[dim]:
+        raise ValueError(f"the range [{lo}, {hi}) of dimension {dim} of shape {shape} (a non-empty range inside the dimension)")
+    rows = inner = 1
+    for s in shape[:dim]:
+        rows *= s
+    for s in shape[dim + 1:]:
+        inner *= s
+    if rows == 0 or inner == 0:
+        raise ValueError(f"a tensor of shape {shape} has no elements")
+    return rows, shape[dim] * inner, 0, rows, lo * inner, hi * inner
+
+
+def _patch_select_public(what, patch, shape, dim, lo, hi, place):
+    from . import _capi
+    try:
+        E, n = _patch_header(patch, "the patch")
+    except ValueError as e:
+        raise ValueError(str(e).replace("patch_merge", what)) from None
+    rect = narrow_rect(shape, dim, lo, hi)
+    covered = (rect[3] - rect[2]) * (rect[5] - rect[4]) if place else rect[0] * rect[1]
+    if E not in (1, 2, 4) or n != covered * E:
+        raise ValueError(f"{what}: the patch covers {n} bytes in elements of {E}; {'the narrowed tensor' if place else 'a tensor of shape ' + str(tuple(shape))} has {covered} elements")
+    if rect[0] * rect[1] >= 1 << 32:
+        raise ValueError(f"{what}: patches cover fewer than 2^32 elements")
+    if patch.data_ptr() % 16:
+        patch = patch.clone()
+    return patch_select_device_batch(_capi.lib(), [(patch, E) + rect], place=place)[0]
+
+
+def patch_select(patch, shape, dim, lo, hi):
+    """The "znp1" patch of a shard, from the patch of the whole tensor: with patch = patch_build(t, base), t and base of `shape`, the result is byte for byte
+    patch_build(t.narrow(dim, lo, hi - lo).contiguous(), base.narrow(dim, lo, hi - lo).contiguous()) — without t or base — or None when nothing changed inside
+    the shard.  The element size is read from the patch's header, whose n must be prod(shape) elements (ValueError).  The input is validated where the select
+    reads it (the header, and the blocks that overlap the shard: ZnError(ZN_E_CORRUPT)); patch_check validates a whole patch."""
+    return _patch_select_public("patch_select", patch, shape, dim, lo, hi, False)
+
+
+def patch_place(patch, shape, dim, lo, hi):
+    """The inverse of patch_select: `patch` covers the narrow(dim, lo, hi - lo) of a tensor of `shape`; the result covers the whole tensor and changes exactly
+    those elements (None for a patch without entries).  patch_select(patch_place(p, ...), ...) is p, and patch_merge of the placed patches
+    of disjoint shards that tile the tensor is the whole tensor's patch.  The input is validated whole on the way (ZnError(ZN_E_CORRUPT))."""
+    return _patch_select_public("patch_place", patch, shape, dim, lo, hi, True)
+
+
 PATCH_BAD_NAMES = ((1, "header"), (2, "first"), (4, "offset"), (8, "value"), (16, "padding"))      # the ZN_PATCH_BAD_* bits of a check verdict
 
 

@@ -173,6 +173,14 @@ void zn_launch_patch_check(const ZnPatchCSeg& one, const ZnPatchCSeg* d_segs, ui
 struct ZnPatchMSeg { const uint8_t* a; uint64_t a_len; const uint8_t* b; uint64_t b_len; uint8_t* out; uint64_t m; uint32_t wg0; uint32_t w0; uint32_t E; uint32_t pad_; };
 void zn_launch_patch_merge_count(const ZnPatchMSeg& one, const ZnPatchMSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_words, uint32_t* d_status, hipStream_t stream);
 void zn_launch_patch_merge_emit(const ZnPatchMSeg& one, const ZnPatchMSeg* d_segs, uint32_t nseg, uint32_t total_wg, const uint32_t* d_words, uint32_t* d_status, hipStream_t stream);
+// ---- a patch restricted to a rectangle of its tensor, and embedded back : zn_patch_select.hip ----
+// One item of a select / place launch: the input patch, where the emit pass writes (16-byte aligned), the WHOLE tensor as R x C elements of E bytes and the
+// rectangle rows [r0, r1) x cols [c0, c1) of it (not empty, inside, R C < 2^32).  SELECT: the input covers the tensor, the output the rectangle; PLACE: the other
+// way round.  Its first workgroup — one per OUTPUT block — and where the output's NB + 1 words start in the launch's scratch words (the scan between the passes is
+// zn_k_patch_scan, over a ZnPatchBSeg table with the output's m and the same w0).  d_status: one word, ZN_DEV_CORRUPT when an input is malformed.
+struct ZnPatchSSeg { const uint8_t* in; uint64_t in_len; uint8_t* out; uint32_t R, C, r0, r1, c0, c1; uint32_t wg0; uint32_t w0; uint32_t E; uint32_t pad_; };
+void zn_launch_patch_select_count(bool place, const ZnPatchSSeg& one, const ZnPatchSSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_words, uint32_t* d_status, hipStream_t stream);
+void zn_launch_patch_select_emit(bool place, const ZnPatchSSeg& one, const ZnPatchSSeg* d_segs, uint32_t nseg, uint32_t total_wg, const uint32_t* d_words, uint32_t* d_status, hipStream_t stream);
 
 // kernel-name log for zn_last_kernels()
 void zn_note_kernel(const char* name);

@@ -266,6 +266,7 @@ class ResidentCheckpoint:
         ft = ResidentCheckpoint.from_state_dict(ft_sd, "cuda:0", base=base, sparse=True)      # tensors with few changed elements are kept as "znp1" patches
         ft.info(n)["delta"], ft.info(n)["patch_entries"]                                          # "sparse", the number of elements that differ
         flat = s3.rebased(base); sw = ft_b.rebased(ft_a)      # the same tensors over another store: a chain flattened, a sibling re-parented — by patch merges
+        mine = ft.sharded(base_shards, {name: (dim, lo, hi)})     # one tensor-parallel rank's narrow() of every tensor, over its shard of the base — patches are selected, not decoded
 
     CONTENT DIGESTS ("zn64-1"; an error-detecting code, not a cryptographic hash) let a store answer whether what it decodes is still what it was built from:
 
@@ -702,6 +703,100 @@ class ResidentCheckpoint:
         keep.append(onto)
         store = type(self)(dev, [entries[name] for name in self._entries], held, keep=keep)
         store._digests = dict(self._digests) if self._digests is not None else None
+        store._metadata = self._metadata
+        return store
+
+    # ---- sharding a variant ----------------------------------------------------------------------------------------
+    def sharded(self, onto, spec):
+        """One tensor-parallel rank's part of this store as a NEW variant store over `onto`, without decoding what is kept as "znp1" patches: a patch is a
+        sorted list of element indices, so the patch of a narrow() of a tensor is a filter and a re-index of the tensor's patch (zn_patch_select_batch_dev,
+        DESIGN §3.13).
+
+            spec = {"q.weight": (0, 512, 1024), "o.weight": (1, 512, 1024)}      # {name: (dim, lo, hi)}; names absent from it are kept whole
+            mine = ft.sharded(base_shards, spec)                                 # base_shards: what from_state_dict accepts as `base`, or None
+            mine.get_tensor("q.weight")                                          # ft's q.weight.narrow(0, 512, 512)
+
+        `onto` stands, for every tensor, for the same narrow of whatever this store's entry is coded over; keeping it at those values is the caller's contract,
+        as with plain base tensors.  Its dtypes and shapes are checked against the shard shapes — a ValueError names every mismatch —, and so is `spec`: a name
+        this store lacks, a dimension or range the tensor does not have.
+        Every "sparse" entry whose name `onto` has goes through ONE batched select call and becomes "sparse" over onto's tensor, or "same" when nothing falls
+        in the shard; a "same" entry becomes "same" over `onto`.  Every other tensor — a delta body, a plain body, a held tensor, a name `onto` lacks, a
+        selected patch not smaller than the shard — is decoded from this store in groups of at most _BUILD_GROUP_BYTES, narrowed, made contiguous and built by
+        from_state_dict(..., base=onto, sparse=True): nothing is refused, the result is always complete.
+        The result has no index and no digests (its content is not the whole tensors'), keeps `onto` alive and nothing else of this store, and is served by
+        every entry point; save_file(sparse=True) and from_file(path, dev, base=onto) round-trip it — shard a delta file once per rank, and each rank loads
+        its own file over its own shard of the base, base digests verified as ever."""
+        dev, lib = self.device, _capi.lib()
+        if isinstance(onto, ResidentCheckpoint) and onto.device != dev:
+            raise ValueError(f"sharded: onto is a store on {dev}, not on {onto.device}")
+        rects, shapes, wrong = {}, {}, []
+        for name, cut in spec.items():
+            if name not in self._entries:
+                wrong.append(f"{name!r}: the store has no such tensor")
+                continue
+            try:
+                dim, lo, hi = cut
+                shape = self._entries[name].shape
+                rects[name] = codec.narrow_rect(shape, dim, lo, hi)
+                dim %= len(shape)
+                shapes[name] = shape[:dim] + (hi - lo,) + shape[dim + 1:]
+            except (ValueError, TypeError) as err:
+                wrong.append(f"{name!r}: {err}")
+        if wrong:
+            raise ValueError("sharded: " + "; ".join(wrong))
+        refs = self._base_items(onto, dev)
+        for name, e in self._entries.items():
+            ref, shape = refs.get(name), shapes.get(name, e.shape)
+            if ref is not None and not ref.fits(e.dtype, shape):
+                wrong.append(f"{name!r}: onto holds {ref.dtype} {list(ref.shape)}, the shard is {e.dtype} {list(shape)}")
+        if wrong:
+            raise ValueError("sharded: " + "; ".join(wrong))
+        coders, plans, select, fallback, entries = {}, {}, [], [], {}
+        for name, e in self._entries.items():
+            ref, shape = refs.get(name), shapes.get(name, e.shape)
+            if ref is None or e.delta not in ("sparse", "same") or not e.nbytes:
+                fallback.append(name)
+                continue
+            head, prm = _frame_params_for(e.dtype, shape, coders=coders)
+            if not ref.decodes_under(prm, coders):                 # (a resident base that holds the shard in other chunks: the build decides)
+                fallback.append(name)
+            elif e.delta == "same":
+                entries[name] = _Entry.same(name, e.dtype, shape, ref, prm, head=head)
+            else:
+                plans[name] = (head, prm)
+                rows = _numel(e.shape)
+                select.append((e.patch, e.P) + (rects[name] if name in rects else (1, rows, 0, 1, 0, rows)))
+        with _device_of(dev):
+            got = codec.patch_select_device_batch(lib, select)     # ONE call for the store
+        small = [(name, p) for name, p in zip(plans, got) if p is not None and p.numel() < _numel(shapes.get(name, self._entries[name].shape)) * self._entries[name].P]
+        views, packed, o = self._pack([p for _, p in small], dev)
+        mine = dict(zip((name for name, _ in small), views))
+        for name, p in zip(plans, got):
+            e, ref, shape = self._entries[name], refs[name], shapes.get(name, self._entries[name].shape)
+            head, prm = plans[name]
+            if name in mine:
+                entries[name] = _Entry.sparse(name, e.dtype, shape, ref, prm, mine[name], head=head)
+            elif p is None:
+                entries[name] = _Entry.same(name, e.dtype, shape, ref, prm, head=head)
+            else:
+                fallback.append(name)                              # a patch that is not smaller than the shard: the build decides what it is kept as
+        for ne in entries.values():
+            ne.restore = ne.base
+        del got, small
+        keep, held = [packed], o
+        order = {n: i for i, n in enumerate(self._entries)}
+        fallback.sort(key=order.__getitem__)
+        for grp in _groups(fallback, lambda name: self._entries[name].nbytes, self._BUILD_GROUP_BYTES):
+            whole = self.get_tensors(grp)
+            part = {name: (whole[name].narrow(spec[name][0], spec[name][1], spec[name][2] - spec[name][1]).contiguous() if name in spec else whole[name]) for name in grp}
+            del whole
+            sub = type(self).from_state_dict(part, dev, base=onto, sparse=True)
+            entries.update(sub._entries)
+            keep += [k for k in sub._keep if k is not onto]
+            held += sub._held
+        if onto is not None:
+            keep.append(onto)
+        store = type(self)(dev, [entries[name] for name in self._entries], held, keep=keep)
         store._metadata = self._metadata
         return store
 
