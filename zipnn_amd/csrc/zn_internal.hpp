@@ -144,44 +144,6 @@ struct ZnDigSeg { const uint8_t* src; uint64_t n; uint32_t wg0; uint32_t slot; }
 void zn_launch_digest(const ZnDigSeg& one, const ZnDigSeg* d_segs, uint32_t nseg, uint32_t total_wg, unsigned long long* d_out, hipStream_t stream);
 uint64_t zn_digest_scalar(const uint8_t* b, size_t n);      // the same value on the host
 
-// ---- changed-element patches ("znp1", include/zipnn_hip.h) : zn_patch.hip ----
-#define ZN_PATCH_BLOCK 65536u                // elements per block — part of the format's DEFINITION
-#define ZN_PATCH_MAGIC 0x31504E5Au           // "ZNP1", little-endian
-// One item of a count / emit launch: m elements of E bytes at src against base; its first workgroup (one per block, none for an empty item); where its NB + 1
-// words start in the launch's scratch words (count: entries of block b; behind the scan: first[]).  patch: where the emit pass writes (16-byte aligned).
-struct ZnPatchBSeg { const uint8_t* src; const uint8_t* base; uint8_t* patch; uint64_t m; uint32_t wg0; uint32_t w0; uint32_t E; uint32_t pad_; };
-// One item of an apply launch: the patch, the tensor it describes (n bytes, E per element), the byte window [byte_lo, byte_hi) and where the window's first byte
-// lies (dst); its first workgroup — one per block the window touches, the first of them block b_lo.
-struct ZnPatchASeg { const uint8_t* patch; uint64_t patch_len; uint64_t n; uint8_t* dst; uint64_t byte_lo, byte_hi; uint32_t wg0; uint32_t E; uint32_t b_lo; uint32_t pad_; };
-__host__ __device__ static inline uint64_t zn_patch_blocks(uint64_t m) { return (m + ZN_PATCH_BLOCK - 1u) / ZN_PATCH_BLOCK; }
-__host__ __device__ static inline uint64_t zn_patch_a1(uint64_t nb) { return (32u + 4u * (nb + 1u) + 15u) & ~15ull; }
-__host__ __device__ static inline uint64_t zn_patch_a2(uint64_t nb, uint64_t T) { return (zn_patch_a1(nb) + 2u * T + 15u) & ~15ull; }
-__host__ __device__ static inline uint64_t zn_patch_total(uint64_t m, uint32_t E, uint64_t T) { return zn_patch_a2(zn_patch_blocks(m), T) + (uint64_t)E * T; }
-// `one` when d_segs == nullptr, else the table (a workgroup finds its item by binary search over wg0).  d_words: the launch's scratch words.
-void zn_launch_patch_count(const ZnPatchBSeg& one, const ZnPatchBSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_words, hipStream_t stream);
-void zn_launch_patch_scan(const ZnPatchBSeg& one, const ZnPatchBSeg* d_segs, uint32_t nseg, uint32_t* d_words, uint64_t* d_totals, hipStream_t stream);    // d_totals[i] = T of item i
-void zn_launch_patch_emit(const ZnPatchBSeg& one, const ZnPatchBSeg* d_segs, uint32_t nseg, uint32_t total_wg, const uint32_t* d_words, hipStream_t stream);
-void zn_launch_patch_apply(const ZnPatchASeg& one, const ZnPatchASeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_status, hipStream_t stream);
-// One item of a check launch (zn_k_patch_check): the patch and the tensor it claims to describe; its first workgroup — one per block, one for a tensor without
-// elements — and its slot of the launch's verdict words: d_words[2 slot] collects the ZN_PATCH_BAD_* bits, d_words[2 slot + 1] receives the header's T.
-struct ZnPatchCSeg { const uint8_t* patch; uint64_t patch_len; uint64_t n; uint32_t wg0; uint32_t E; uint32_t slot; uint32_t pad_; };
-void zn_launch_patch_check(const ZnPatchCSeg& one, const ZnPatchCSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_words, hipStream_t stream);
-// ---- the XOR-merge of two patches : zn_patch_merge.hip ----
-// One item of a merge launch: the two patches of one tensor of m elements of E bytes, where the emit pass writes (16-byte aligned); its first workgroup — one per
-// block, one for a tensor without elements — and where its NB + 1 words start in the launch's scratch words (as ZnPatchBSeg's: the scan between the passes is
-// zn_k_patch_scan, over a ZnPatchBSeg table with the same m and w0).  d_status: one word, ZN_DEV_CORRUPT when an input is malformed.
-struct ZnPatchMSeg { const uint8_t* a; uint64_t a_len; const uint8_t* b; uint64_t b_len; uint8_t* out; uint64_t m; uint32_t wg0; uint32_t w0; uint32_t E; uint32_t pad_; };
-void zn_launch_patch_merge_count(const ZnPatchMSeg& one, const ZnPatchMSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_words, uint32_t* d_status, hipStream_t stream);
-void zn_launch_patch_merge_emit(const ZnPatchMSeg& one, const ZnPatchMSeg* d_segs, uint32_t nseg, uint32_t total_wg, const uint32_t* d_words, uint32_t* d_status, hipStream_t stream);
-// ---- a patch restricted to a rectangle of its tensor, and embedded back : zn_patch_select.hip ----
-// One item of a select / place launch: the input patch, where the emit pass writes (16-byte aligned), the WHOLE tensor as R x C elements of E bytes and the
-// rectangle rows [r0, r1) x cols [c0, c1) of it (not empty, inside, R C < 2^32).  SELECT: the input covers the tensor, the output the rectangle; PLACE: the other
-// way round.  Its first workgroup — one per OUTPUT block — and where the output's NB + 1 words start in the launch's scratch words (the scan between the passes is
-// zn_k_patch_scan, over a ZnPatchBSeg table with the output's m and the same w0).  d_status: one word, ZN_DEV_CORRUPT when an input is malformed.
-struct ZnPatchSSeg { const uint8_t* in; uint64_t in_len; uint8_t* out; uint32_t R, C, r0, r1, c0, c1; uint32_t wg0; uint32_t w0; uint32_t E; uint32_t pad_; };
-void zn_launch_patch_select_count(bool place, const ZnPatchSSeg& one, const ZnPatchSSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_words, uint32_t* d_status, hipStream_t stream);
-void zn_launch_patch_select_emit(bool place, const ZnPatchSSeg& one, const ZnPatchSSeg* d_segs, uint32_t nseg, uint32_t total_wg, const uint32_t* d_words, uint32_t* d_status, hipStream_t stream);
-
 // kernel-name log for zn_last_kernels()
 void zn_note_kernel(const char* name);
 

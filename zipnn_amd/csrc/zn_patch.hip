@@ -12,39 +12,20 @@
 // ranks ascend with the thread index: a wave-exclusive scan of the per-thread counts, the waves' sums through LDS, a running total in a register.
 // The apply kernel trusts nothing: a patch may come from anywhere.  It reads only inside [patch, patch + patch_len) — the header first, whose L must be patch_len
 // and the formula's value for its T, which bounds every later index — and writes only elements of the window; what is wrong costs the verdict (ZN_DEV_CORRUPT).
-#include "zn_workspace.hpp"
+#include "zn_patch_host.hpp"
 
 #include <memory>
-#include <vector>
 
-#define ZN_PA_THREADS 256u
-#define ZN_PA_WAVES (ZN_PA_THREADS / 64u)
-
-template <uint32_t E> struct ZnPaElem;
-template <> struct ZnPaElem<1> { typedef uint8_t t; };
-template <> struct ZnPaElem<2> { typedef uint16_t t; };
-template <> struct ZnPaElem<4> { typedef uint32_t t; };
-
-template <typename S>
-__device__ __forceinline__ S zn_pa_find(const S& one, const S* __restrict__ segs, uint32_t nseg, uint32_t b) {
-  if (segs == nullptr) return one;
-  uint32_t lo = 0, hi = nseg;
-  while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (segs[mid].wg0 <= b) lo = mid; else hi = mid; }
-  return segs[lo];
-}
-
-// inclusive sum over the lanes of a wave (lane 63 holds the wave's total); skipped where no lane of the wave brings anything
+// zn_patch_wave_incl, skipped where no lane of the wave brings anything
 __device__ __forceinline__ uint32_t zn_pa_wave_incl(uint32_t v, uint32_t lane) {
   if (__ballot(v != 0u) == 0ull) return 0u;
-#pragma unroll
-  for (uint32_t d = 1; d < 64u; d <<= 1) { const uint32_t t = __shfl_up(v, d); if (lane >= d) v += t; }
-  return v;
+  return zn_patch_wave_incl(v, lane);
 }
 
 // src ^ base of the 16 / E elements from element e0 on, as the four little-endian words they occupy (elements at or behind m: zero) -> the mask of those that differ
 template <uint32_t E>
 __device__ __forceinline__ uint32_t zn_pa_diff(const uint8_t* __restrict__ src, const uint8_t* __restrict__ base, uint64_t e0, uint64_t m, bool fast, uint32_t (&x)[4]) {
-  typedef typename ZnPaElem<E>::t T;
+  typedef typename ZnPatchElem<E>::t T;
   constexpr uint32_t V = 16u / E;
   if (fast && e0 + V <= m) {
     const uint4 a = *(const uint4*)(src + e0 * E), b = *(const uint4*)(base + e0 * E);
@@ -69,9 +50,9 @@ __device__ __forceinline__ uint32_t zn_pa_diff(const uint8_t* __restrict__ src, 
 
 // Block b of one item.  !EMIT: words[b] = its number of differing elements.  EMIT: words[] is first[]; the block's entries go to off / val of the patch.
 template <uint32_t E, bool EMIT>
-__device__ __forceinline__ void zn_pa_block(const ZnPatchBSeg& sg, uint32_t b, uint32_t* __restrict__ words, uint32_t (*part)[ZN_PA_WAVES]) {
-  typedef typename ZnPaElem<E>::t T;
-  constexpr uint32_t V = 16u / E, STEP = ZN_PA_THREADS * V;
+__device__ __forceinline__ void zn_pa_block(const ZnPatchBSeg& sg, uint32_t b, uint32_t* __restrict__ words, uint32_t (*part)[ZN_PATCH_WAVES]) {
+  typedef typename ZnPatchElem<E>::t T;
+  constexpr uint32_t V = 16u / E, STEP = ZN_PATCH_THREADS * V;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint8_t* src = ZN_GLOBAL_PTR(const uint8_t, sg.src);
   const uint8_t* base = ZN_GLOBAL_PTR(const uint8_t, sg.base);
@@ -84,21 +65,10 @@ __device__ __forceinline__ void zn_pa_block(const ZnPatchBSeg& sg, uint32_t b, u
   if (EMIT) {
     const uint64_t nb = zn_patch_blocks(m), total = words[nb];
     uint8_t* p = ZN_GLOBAL_PTR(uint8_t, sg.patch);
-    const uint64_t a1 = zn_patch_a1(nb), a2 = zn_patch_a2(nb, total);
     lo = words[b]; hi = words[b + 1u];
-    if (tid == 0) {
-      uint32_t* first = (uint32_t*)(p + 32);
-      first[b] = lo;
-      if (b + 1u == nb) first[nb] = (uint32_t)total;
-      if (b == 0) {                              // the header, and the zero padding in front of off[] and of val[]
-        *(uint32_t*)p = ZN_PATCH_MAGIC; *(uint32_t*)(p + 4) = E;
-        *(uint64_t*)(p + 8) = m * E; *(uint64_t*)(p + 16) = total; *(uint64_t*)(p + 24) = a2 + (uint64_t)E * total;
-        for (uint64_t i = 32u + 4u * (nb + 1u); i < a1; i++) p[i] = 0;
-        for (uint64_t i = a1 + 2u * total; i < a2; i++) p[i] = 0;
-      }
-    }
+    if (tid == 0) zn_patch_emit_head<E>(p, m, nb, total, b, lo);
     if (hi <= lo) return;                        // (workgroup-uniform) nothing of this block differs
-    off = (uint16_t*)(p + a1); val = (T*)(p + a2);
+    off = (uint16_t*)(p + zn_patch_a1(nb)); val = (T*)(p + zn_patch_a2(nb, total));
   }
   uint32_t run = 0;                              // count: this thread's differing elements; emit: the block's entries in front of this step
   for (uint32_t s = 0; s < steps; s++) {
@@ -110,9 +80,8 @@ __device__ __forceinline__ void zn_pa_block(const ZnPatchBSeg& sg, uint32_t b, u
     const uint32_t incl = zn_pa_wave_incl(cnt, lane);
     if (lane == 63u) part[s & 1u][wave] = incl;  // (two sets of slots: one barrier per step is enough)
     __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < ZN_PA_WAVES; w++) { const uint32_t q = part[s & 1u][w]; if (w < wave) before += q; all += q; }
+    uint32_t before, all;
+    zn_patch_wave_sums(part[s & 1u], wave, before, all);
     if (cnt) {
       uint32_t pos = lo + run + before + incl - cnt;
 #pragma unroll
@@ -133,14 +102,14 @@ __device__ __forceinline__ void zn_pa_block(const ZnPatchBSeg& sg, uint32_t b, u
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
     if (lane == 0) part[0][wave] = v;
     __syncthreads();
-    if (tid == 0) { uint32_t c = 0; for (uint32_t w = 0; w < ZN_PA_WAVES; w++) c += part[0][w]; words[b] = c; }
+    if (tid == 0) { uint32_t c = 0; for (uint32_t w = 0; w < ZN_PATCH_WAVES; w++) c += part[0][w]; words[b] = c; }
   }
 }
 
 template <bool EMIT>
-__device__ __forceinline__ void zn_pa_dispatch(const ZnPatchBSeg& one, const ZnPatchBSeg* __restrict__ segs_, uint32_t nseg, uint32_t* words_, uint32_t (*part)[ZN_PA_WAVES]) {
+__device__ __forceinline__ void zn_pa_dispatch(const ZnPatchBSeg& one, const ZnPatchBSeg* __restrict__ segs_, uint32_t nseg, uint32_t* words_, uint32_t (*part)[ZN_PATCH_WAVES]) {
   const ZnPatchBSeg* segs = ZN_GLOBAL_PTR(const ZnPatchBSeg, segs_);
-  const ZnPatchBSeg sg = zn_pa_find(one, segs, nseg, blockIdx.x);
+  const ZnPatchBSeg sg = zn_patch_find(one, segs, nseg, blockIdx.x);
   uint32_t* words = ZN_GLOBAL_PTR(uint32_t, words_) + sg.w0;
   const uint32_t b = blockIdx.x - sg.wg0;
   if (sg.E == 1u) zn_pa_block<1, EMIT>(sg, b, words, part);
@@ -148,34 +117,34 @@ __device__ __forceinline__ void zn_pa_dispatch(const ZnPatchBSeg& one, const ZnP
   else zn_pa_block<4, EMIT>(sg, b, words, part);
 }
 
-__global__ void __launch_bounds__(ZN_PA_THREADS) zn_k_patch_count(const ZnPatchBSeg one, const ZnPatchBSeg* __restrict__ segs, uint32_t nseg, uint32_t* __restrict__ words) {
-  __shared__ uint32_t part[2][ZN_PA_WAVES];
+__global__ void __launch_bounds__(ZN_PATCH_THREADS) zn_k_patch_count(const ZnPatchBSeg one, const ZnPatchBSeg* __restrict__ segs, uint32_t nseg, uint32_t* __restrict__ words) {
+  __shared__ uint32_t part[2][ZN_PATCH_WAVES];
   zn_pa_dispatch<false>(one, segs, nseg, words, part);
 }
 
-__global__ void __launch_bounds__(ZN_PA_THREADS) zn_k_patch_emit(const ZnPatchBSeg one, const ZnPatchBSeg* __restrict__ segs, uint32_t nseg, uint32_t* __restrict__ words) {
-  __shared__ uint32_t part[2][ZN_PA_WAVES];
+__global__ void __launch_bounds__(ZN_PATCH_THREADS) zn_k_patch_emit(const ZnPatchBSeg one, const ZnPatchBSeg* __restrict__ segs, uint32_t nseg, uint32_t* __restrict__ words) {
+  __shared__ uint32_t part[2][ZN_PATCH_WAVES];
   zn_pa_dispatch<true>(one, segs, nseg, words, part);
 }
 
 // one workgroup per item: its block counts -> first[] (in place), first[NB] = T, totals[item] = T
-__global__ void __launch_bounds__(ZN_PA_THREADS) zn_k_patch_scan(const ZnPatchBSeg one, const ZnPatchBSeg* __restrict__ segs_, uint32_t* __restrict__ words_, uint64_t* __restrict__ totals) {
-  __shared__ uint32_t part[ZN_PA_WAVES];
+__global__ void __launch_bounds__(ZN_PATCH_THREADS) zn_k_patch_scan(const ZnPatchBSeg one, const ZnPatchBSeg* __restrict__ segs_, uint32_t* __restrict__ words_, uint64_t* __restrict__ totals) {
+  __shared__ uint32_t part[ZN_PATCH_WAVES];
   const ZnPatchBSeg* segs = ZN_GLOBAL_PTR(const ZnPatchBSeg, segs_);
   const ZnPatchBSeg sg = segs ? segs[blockIdx.x] : one;
   uint32_t* words = ZN_GLOBAL_PTR(uint32_t, words_) + sg.w0;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint32_t nb = (uint32_t)zn_patch_blocks(sg.m);
   uint32_t run = 0;
-  for (uint32_t i0 = 0; i0 < nb; i0 += ZN_PA_THREADS) {
+  for (uint32_t i0 = 0; i0 < nb; i0 += ZN_PATCH_THREADS) {
     const uint32_t i = i0 + tid;
     const uint32_t c = i < nb ? words[i] : 0u;
     const uint32_t incl = zn_pa_wave_incl(c, lane);
     if (lane == 63u) part[wave] = incl;
     __syncthreads();
-    uint32_t before = 0, all = 0;
+    uint32_t before = 0, all = 0;                // (zn_patch_wave_sums, written out: through the helper this kernel takes a 29th vector register)
 #pragma unroll
-    for (uint32_t w = 0; w < ZN_PA_WAVES; w++) { const uint32_t q = part[w]; if (w < wave) before += q; all += q; }
+    for (uint32_t w = 0; w < ZN_PATCH_WAVES; w++) { const uint32_t q = part[w]; if (w < wave) before += q; all += q; }
     if (i < nb) words[i] = run + before + incl - c;
     run += all;
     __syncthreads();
@@ -185,20 +154,17 @@ __global__ void __launch_bounds__(ZN_PA_THREADS) zn_k_patch_scan(const ZnPatchBS
 
 template <uint32_t E>
 __device__ __forceinline__ void zn_pa_apply_block(const ZnPatchASeg& sg, uint32_t b, uint32_t* __restrict__ status) {
-  typedef typename ZnPaElem<E>::t T;
+  typedef typename ZnPatchElem<E>::t T;
   const uint32_t tid = threadIdx.x;
   const uint8_t* p = ZN_GLOBAL_PTR(const uint8_t, sg.patch);
   const uint64_t n = sg.n, m = n / E, nb = zn_patch_blocks(m);                   // (the host has checked: n % E == 0, m < 2^32, patch_len >= 32, b < nb)
-  // the header must describe this item, and its L — the formula's value for its T — must be the length we were given: every index below T then lies inside
-  const uint32_t magic = *(const uint32_t*)p, e = *(const uint32_t*)(p + 4);
-  const uint64_t hn = *(const uint64_t*)(p + 8), total = *(const uint64_t*)(p + 16), len = *(const uint64_t*)(p + 24);
-  bool bad = magic != ZN_PATCH_MAGIC || e != E || hn != n || total > m || len != sg.patch_len;
-  if (!bad) bad = zn_patch_total(m, E, total) != len;
+  uint64_t total;
+  bool bad = !zn_patch_header_ok<E>(zn_patch_header(p), n, m, sg.patch_len, total);
   uint32_t f0 = 0, f1 = 0;
   if (!bad) {
     const uint32_t* first = (const uint32_t*)(p + 32);
     f0 = first[b]; f1 = first[b + 1u];
-    bad = f0 > f1 || (uint64_t)f1 > total || (b == 0 && f0 != 0u) || (b + 1u == nb && (uint64_t)f1 != total);
+    bad = zn_patch_pair_bad(f0, f1, total, b, nb);
   }
   if (bad) {                                     // (workgroup-uniform)
     if (tid == 0) atomicOr(status, ZN_DEV_CORRUPT);
@@ -209,39 +175,41 @@ __device__ __forceinline__ void zn_pa_apply_block(const ZnPatchASeg& sg, uint32_
   T* dst = (T*)ZN_GLOBAL_PTR(uint8_t, sg.dst);
   const uint64_t e_lo = sg.byte_lo / E, e_hi = sg.byte_hi / E, blk0 = (uint64_t)b * ZN_PATCH_BLOCK;
   bool wrong = false;
-  for (uint32_t i = f0 + tid; i < f1; i += ZN_PA_THREADS) {
+  for (uint32_t i = f0 + tid; i < f1; i += ZN_PATCH_THREADS) {
     const uint32_t o = off[i];
     const T v = val[i];
     const uint64_t el = blk0 + o;
-    if (el >= m || v == (T)0 || (i > f0 && (uint32_t)off[i - 1u] >= o)) { wrong = true; continue; }
+    if (zn_patch_entry_bad(off, i, f0, o, v, el, m)) { wrong = true; continue; }
     if (el >= e_lo && el < e_hi) dst[el - e_lo] ^= v;
   }
   if (wrong) atomicOr(status, ZN_DEV_CORRUPT);
 }
 
-__global__ void __launch_bounds__(ZN_PA_THREADS) zn_k_patch_apply(const ZnPatchASeg one, const ZnPatchASeg* __restrict__ segs_, uint32_t nseg, uint32_t* __restrict__ status) {
+__global__ void __launch_bounds__(ZN_PATCH_THREADS) zn_k_patch_apply(const ZnPatchASeg one, const ZnPatchASeg* __restrict__ segs_, uint32_t nseg, uint32_t* __restrict__ status) {
   const ZnPatchASeg* segs = ZN_GLOBAL_PTR(const ZnPatchASeg, segs_);
-  const ZnPatchASeg sg = zn_pa_find(one, segs, nseg, blockIdx.x);
+  const ZnPatchASeg sg = zn_patch_find(one, segs, nseg, blockIdx.x);
   const uint32_t b = sg.b_lo + (blockIdx.x - sg.wg0);
   if (sg.E == 1u) zn_pa_apply_block<1>(sg, b, status);
   else if (sg.E == 2u) zn_pa_apply_block<2>(sg, b, status);
   else zn_pa_apply_block<4>(sg, b, status);
 }
 
-// ---- zn_k_patch_check: is the WHOLE patch well-formed?  Apply's checks restated (zn_pa_apply_block stays what it is) for every block and every entry, and the
-// canonical form apply never reads.  Reads [patch, patch + patch_len) — the header first, which bounds every later index, as in apply — and writes verdict words.
+// ---- zn_k_patch_check: is the WHOLE patch well-formed?  Apply's header test (written out, below) and first[] test (zn_patch_format.hpp) for every block, its entry rules for
+// every entry with a finding of their own each, and the canonical form apply never reads.  Reads [patch, patch + patch_len) — the header first, which bounds every later index, as in apply — and writes verdict words.
 // A thread takes 8 consecutive entries per step: one 16-byte load of off[] (groups start at multiples of 8 entries; off[] is padded to a multiple of 16 bytes, so
 // a group that holds an entry lies inside the patch) and the 8 E bytes of val[] in 8- or 16-byte loads where all 8 are entries (val[] has no padding behind it).
 struct alignas(16) ZnPcOffs { uint16_t o[8]; };
-template <uint32_t E> struct alignas(E == 1u ? 8 : 16) ZnPcVals { typename ZnPaElem<E>::t v[8]; };
+template <uint32_t E> struct alignas(E == 1u ? 8 : 16) ZnPcVals { typename ZnPatchElem<E>::t v[8]; };
 
 template <uint32_t E>
 __device__ __forceinline__ void zn_pc_block(const ZnPatchCSeg& sg, uint32_t b, uint32_t* __restrict__ words) {
-  typedef typename ZnPaElem<E>::t T;
+  typedef typename ZnPatchElem<E>::t T;
   const uint32_t tid = threadIdx.x;
   const uint8_t* p = ZN_GLOBAL_PTR(const uint8_t, sg.patch);
   uint32_t* verdict = words + 2u * sg.slot;
   const uint64_t n = sg.n, m = n / E, nb = zn_patch_blocks(m);                   // (the host has checked: n % E == 0, m < 2^32, patch_len >= 32, b < max(nb, 1))
+  // zn_patch_header_ok's test, written out: E is the byte p[4] here — what lies in bytes 5 - 7 is a finding about the padding (below), not about the header —, and
+  // through zn_patch_header this kernel takes 52 vector registers instead of 50
   const uint32_t magic = *(const uint32_t*)p, e = p[4];
   const uint64_t hn = *(const uint64_t*)(p + 8), total = *(const uint64_t*)(p + 16), len = *(const uint64_t*)(p + 24);
   bool bad = magic != ZN_PATCH_MAGIC || e != E || hn != n || total > m || len != sg.patch_len;
@@ -261,12 +229,12 @@ __device__ __forceinline__ void zn_pc_block(const ZnPatchCSeg& sg, uint32_t b, u
   }
   const uint32_t* first = (const uint32_t*)(p + 32);
   const uint32_t f0 = first[b], f1 = nb ? first[b + 1u] : f0;                    // (a tensor without elements: first[0] alone, and T == 0)
-  if (f0 > f1 || (uint64_t)f1 > total || (b == 0 && f0 != 0u) || ((uint64_t)b + 1u >= nb && (uint64_t)f1 != total)) found |= ZN_PATCH_BAD_FIRST;      // (workgroup-uniform)
+  if (zn_patch_pair_bad(f0, f1, total, b, nb)) found |= ZN_PATCH_BAD_FIRST;      // (workgroup-uniform; nb == 0: T == 0 behind the header test, and f1 is f0, which must be 0)
   else {
     const uint16_t* off = (const uint16_t*)(p + a1);
     const T* val = (const T*)(p + a2);
     const uint64_t blk0 = (uint64_t)b * ZN_PATCH_BLOCK;
-    for (uint64_t g = (uint64_t)(f0 & ~7u) + 8u * tid; g < f1; g += 8u * ZN_PA_THREADS) {
+    for (uint64_t g = (uint64_t)(f0 & ~7u) + 8u * tid; g < f1; g += 8u * ZN_PATCH_THREADS) {
       const ZnPcOffs og = *(const ZnPcOffs*)(off + g);
       ZnPcVals<E> vg;
       if (g + 8u <= total) vg = *(const ZnPcVals<E>*)(val + g);
@@ -294,9 +262,9 @@ __device__ __forceinline__ void zn_pc_block(const ZnPatchCSeg& sg, uint32_t b, u
   if ((tid & 63u) == 0 && found) atomicOr(verdict, found);                       // (at most one per wave)
 }
 
-__global__ void __launch_bounds__(ZN_PA_THREADS) zn_k_patch_check(const ZnPatchCSeg one, const ZnPatchCSeg* __restrict__ segs_, uint32_t nseg, uint32_t* __restrict__ words_) {
+__global__ void __launch_bounds__(ZN_PATCH_THREADS) zn_k_patch_check(const ZnPatchCSeg one, const ZnPatchCSeg* __restrict__ segs_, uint32_t nseg, uint32_t* __restrict__ words_) {
   const ZnPatchCSeg* segs = ZN_GLOBAL_PTR(const ZnPatchCSeg, segs_);
-  const ZnPatchCSeg sg = zn_pa_find(one, segs, nseg, blockIdx.x);
+  const ZnPatchCSeg sg = zn_patch_find(one, segs, nseg, blockIdx.x);
   uint32_t* words = ZN_GLOBAL_PTR(uint32_t, words_);
   const uint32_t b = blockIdx.x - sg.wg0;
   if (sg.E == 1u) zn_pc_block<1>(sg, b, words);
@@ -306,46 +274,37 @@ __global__ void __launch_bounds__(ZN_PA_THREADS) zn_k_patch_check(const ZnPatchC
 
 void zn_launch_patch_count(const ZnPatchBSeg& one, const ZnPatchBSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_words, hipStream_t stream) {
   if (nseg == 0 || total_wg == 0) return;
-  hipLaunchKernelGGL(zn_k_patch_count, dim3(total_wg), dim3(ZN_PA_THREADS), 0, stream, one, d_segs, nseg, d_words);
+  hipLaunchKernelGGL(zn_k_patch_count, dim3(total_wg), dim3(ZN_PATCH_THREADS), 0, stream, one, d_segs, nseg, d_words);
   zn_note_kernel("zn_k_patch_count");
 }
 void zn_launch_patch_scan(const ZnPatchBSeg& one, const ZnPatchBSeg* d_segs, uint32_t nseg, uint32_t* d_words, uint64_t* d_totals, hipStream_t stream) {
   if (nseg == 0) return;
-  hipLaunchKernelGGL(zn_k_patch_scan, dim3(nseg), dim3(ZN_PA_THREADS), 0, stream, one, d_segs, d_words, d_totals);
+  hipLaunchKernelGGL(zn_k_patch_scan, dim3(nseg), dim3(ZN_PATCH_THREADS), 0, stream, one, d_segs, d_words, d_totals);
   zn_note_kernel("zn_k_patch_scan");
 }
 void zn_launch_patch_emit(const ZnPatchBSeg& one, const ZnPatchBSeg* d_segs, uint32_t nseg, uint32_t total_wg, const uint32_t* d_words, hipStream_t stream) {
   if (nseg == 0 || total_wg == 0) return;
-  hipLaunchKernelGGL(zn_k_patch_emit, dim3(total_wg), dim3(ZN_PA_THREADS), 0, stream, one, d_segs, nseg, const_cast<uint32_t*>(d_words));
+  hipLaunchKernelGGL(zn_k_patch_emit, dim3(total_wg), dim3(ZN_PATCH_THREADS), 0, stream, one, d_segs, nseg, const_cast<uint32_t*>(d_words));
   zn_note_kernel("zn_k_patch_emit");
 }
 void zn_launch_patch_apply(const ZnPatchASeg& one, const ZnPatchASeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_status, hipStream_t stream) {
   if (nseg == 0 || total_wg == 0) return;
-  hipLaunchKernelGGL(zn_k_patch_apply, dim3(total_wg), dim3(ZN_PA_THREADS), 0, stream, one, d_segs, nseg, d_status);
+  hipLaunchKernelGGL(zn_k_patch_apply, dim3(total_wg), dim3(ZN_PATCH_THREADS), 0, stream, one, d_segs, nseg, d_status);
   zn_note_kernel("zn_k_patch_apply");
 }
 void zn_launch_patch_check(const ZnPatchCSeg& one, const ZnPatchCSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_words, hipStream_t stream) {
   if (nseg == 0 || total_wg == 0) return;
-  hipLaunchKernelGGL(zn_k_patch_check, dim3(total_wg), dim3(ZN_PA_THREADS), 0, stream, one, d_segs, nseg, d_words);
+  hipLaunchKernelGGL(zn_k_patch_check, dim3(total_wg), dim3(ZN_PATCH_THREADS), 0, stream, one, d_segs, nseg, d_words);
   zn_note_kernel("zn_k_patch_check");
 }
 
 // ---- the C ABI of the patches (host side: checks, tables, launches) ----
 namespace {
 
-bool patch_elem_ok(size_t n, int elem) { return (elem == 1 || elem == 2 || elem == 4) && n % (size_t)elem == 0 && (uint64_t)(n / (size_t)elem) < (1ull << 32); }
 bool patch_aligned(const void* p, int elem) { return (((uintptr_t)p) & (uintptr_t)(elem - 1)) == 0; }
 
-// a table of `count` entries of S through the pinned staging buffer into WS_SEGS at byte offset `at`; the caller has synchronised with the buffer's last reader
-template <typename S>
-int patch_stage(Workspace& w, const std::vector<S>& segs, size_t at, hipStream_t stream) {
-  const size_t bytes = segs.size() * sizeof(S);
-  memcpy((uint8_t*)w.h_segs.p + at, segs.data(), bytes);
-  ZN_HIP(hipMemcpyAsync((uint8_t*)w.buf[WS_SEGS] + at, (uint8_t*)w.h_segs.p + at, bytes, hipMemcpyHostToDevice, stream));
-  return ZN_OK;
-}
-
-// Count, scan, one read-back of every item's T; with `emit`: capacity check, then the emit pass for the items that differ.  Synchronous.
+// The sizes of the patches of `items` against their bases; with `emit`: … and the patches, where every capacity suffices (zn_patch_two_pass).  An item without
+// elements gets no workgroup; lens[i] == 0: the tensor's bytes are the base's.
 struct PatchSrc { const void* d_src; const void* d_base; size_t n; int elem; void* d_patch; size_t cap; };
 int patch_build(const std::vector<PatchSrc>& items, std::vector<uint64_t>& lens, bool emit, hipStream_t stream) {
   const size_t count = items.size();
@@ -353,60 +312,22 @@ int patch_build(const std::vector<PatchSrc>& items, std::vector<uint64_t>& lens,
   if (count == 0) return ZN_OK;
   if (count > 0x7FFFFFFFull) return ZN_E_ARG;
   std::vector<ZnPatchBSeg> segs(count);
+  std::vector<size_t> caps(count);
   uint64_t wg = 0, words = 0;
   for (size_t i = 0; i < count; i++) {
     const PatchSrc& it = items[i];
-    if (!patch_elem_ok(it.n, it.elem)) return ZN_E_ARG;
+    if (!zn_patch_elem_ok(it.n, it.elem)) return ZN_E_ARG;
     if (it.n && (!it.d_src || !it.d_base || !patch_aligned(it.d_src, it.elem) || !patch_aligned(it.d_base, it.elem))) return ZN_E_ARG;
-    if (emit && it.cap && (!it.d_patch || (((uintptr_t)it.d_patch) & 15u) != 0)) return ZN_E_ARG;
+    if (emit && it.cap && !zn_patch_out_ok(it.d_patch)) return ZN_E_ARG;
     const uint64_t m = it.n / (size_t)it.elem;
     segs[i] = ZnPatchBSeg{(const uint8_t*)it.d_src, (const uint8_t*)it.d_base, (uint8_t*)it.d_patch, m, (uint32_t)wg, (uint32_t)words, (uint32_t)it.elem, 0u};
+    caps[i] = it.cap;
     wg += zn_patch_blocks(m); words += zn_patch_blocks(m) + 1u;
     if (wg > 0x7FFFFFFFull || words > 0x7FFFFFFFull) return ZN_E_ARG;
   }
-  WsLease L;
-  if (L.rc) return L.rc;
-  Workspace& w = *L.w;
-  t_kernels.clear();
-  int rc;
-  const bool table = count > 1;
-  const size_t table_bytes = table ? count * sizeof(ZnPatchBSeg) : 0u;          // (twice: the emit pass has a grid of its own)
-  if ((rc = w.reserve(WS_META_A, words * sizeof(uint32_t)))) return rc;
-  if ((rc = w.reserve(WS_TOTALS, count * sizeof(uint64_t)))) return rc;
-  if ((rc = w.h_totals.reserve(count * sizeof(uint64_t)))) return rc;
-  if (table && (rc = w.reserve(WS_SEGS, 2u * table_bytes))) return rc;
-  if ((rc = L.acquire(stream))) return rc;
-  L.mark = table;
-  if (table) {
-    ZN_HIP(hipEventSynchronize(w.busy));         // the previous batched call may still be reading the pinned staging
-    if ((rc = w.h_segs.reserve(2u * table_bytes))) return rc;
-    if ((rc = patch_stage(w, segs, 0, stream))) return rc;
-  }
-  const ZnPatchBSeg* d_segs = table ? (const ZnPatchBSeg*)w.buf[WS_SEGS] : nullptr;
-  uint32_t* d_words = (uint32_t*)w.buf[WS_META_A];
-  uint64_t* d_totals = (uint64_t*)w.buf[WS_TOTALS];
-  zn_launch_patch_count(segs[0], d_segs, (uint32_t)count, (uint32_t)wg, d_words, stream);
-  zn_launch_patch_scan(segs[0], d_segs, (uint32_t)count, d_words, d_totals, stream);
-  if (launch_failed()) return ZN_E_HIP;
-  ZN_HIP(hipMemcpyAsync(w.h_totals.p, d_totals, count * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-  ZN_HIP(hipStreamSynchronize(stream));
-  const uint64_t* T = (const uint64_t*)w.h_totals.p;
-  bool short_cap = false;
-  for (size_t i = 0; i < count; i++) {
-    lens[i] = T[i] ? zn_patch_total(segs[i].m, segs[i].E, T[i]) : 0u;           // (0: the tensor's bytes are the base's)
-    if (emit && lens[i] > items[i].cap) short_cap = true;
-  }
-  if (!emit) return ZN_OK;
-  if (short_cap) return ZN_E_CAP;
-  uint64_t ewg = 0;
-  for (size_t i = 0; i < count; i++) { segs[i].wg0 = (uint32_t)ewg; if (T[i]) ewg += zn_patch_blocks(segs[i].m); }
-  if (ewg == 0) return ZN_OK;
-  // (the first table's copy is over — the stream was synchronised —; the emit table goes behind it)
-  if (table && (rc = patch_stage(w, segs, table_bytes, stream))) return rc;
-  zn_launch_patch_emit(segs[0], table ? (const ZnPatchBSeg*)((const uint8_t*)w.buf[WS_SEGS] + table_bytes) : nullptr, (uint32_t)count, (uint32_t)ewg, d_words, stream);
-  if (launch_failed()) return ZN_E_HIP;
-  ZN_HIP(hipStreamSynchronize(stream));
-  return ZN_OK;
+  return zn_patch_two_pass(segs, segs.data(), wg, words, emit ? caps.data() : nullptr, lens, stream,
+                           [](const ZnPatchBSeg& one, const ZnPatchBSeg* d, uint32_t n, uint32_t g, uint32_t* wd, uint32_t*, hipStream_t st) { zn_launch_patch_count(one, d, n, g, wd, st); },
+                           [](const ZnPatchBSeg& one, const ZnPatchBSeg* d, uint32_t n, uint32_t g, uint32_t* wd, uint32_t*, hipStream_t st) { zn_launch_patch_emit(one, d, n, g, wd, st); });
 }
 
 // what an apply call or plan works out before its first launch
@@ -422,9 +343,9 @@ int patch_apply_segments(const zn_patch_apply_item* items, size_t count, PatchAp
   A.segs.resize(count);
   for (size_t i = 0; i < count; i++) {
     const zn_patch_apply_item& it = items[i];
-    if (!patch_elem_ok(it.n, it.elem)) return ZN_E_ARG;
+    if (!zn_patch_elem_ok(it.n, it.elem)) return ZN_E_ARG;
     const size_t E = (size_t)it.elem;
-    if (!it.d_patch || (((uintptr_t)it.d_patch) & 15u) != 0 || it.patch_len < 32u) return ZN_E_ARG;
+    if (!zn_patch_input_ok(it.d_patch, it.patch_len)) return ZN_E_ARG;
     if (it.byte_lo > it.byte_hi || it.byte_hi > it.n || it.byte_lo % E || it.byte_hi % E) return ZN_E_ARG;
     const bool empty = it.byte_lo == it.byte_hi;
     if (!empty && (!it.d_dst || !patch_aligned(it.d_dst, it.elem))) return ZN_E_ARG;
@@ -460,7 +381,7 @@ int patch_apply_launch(const PatchApplySet& A, const ZnPatchASeg* d_table, hipSt
   if (staged) {
     ZN_HIP(hipEventSynchronize(w.busy));         // the previous batched call may still be reading the pinned staging
     if ((rc = w.h_segs.reserve(table_bytes))) return rc;
-    if ((rc = patch_stage(w, A.segs, 0, stream))) return rc;
+    if ((rc = zn_patch_stage(w, A.segs.data(), table_bytes, 0, stream))) return rc;
     d_table = (const ZnPatchASeg*)w.buf[WS_SEGS];
   }
   if (A.total_wg) zn_launch_patch_apply(A.segs[0], A.segs.size() > 1 ? d_table : nullptr, (uint32_t)A.segs.size(), (uint32_t)A.total_wg, d_status, stream);
@@ -491,7 +412,7 @@ struct zn_patch_plan {
 extern "C" {
 
 size_t zn_patch_len(size_t n, int elem, size_t entries) {
-  if (!patch_elem_ok(n, elem) || entries > n / (size_t)elem) return 0;
+  if (!zn_patch_elem_ok(n, elem) || entries > n / (size_t)elem) return 0;
   return (size_t)zn_patch_total(n / (size_t)elem, (uint32_t)elem, entries);
 }
 
@@ -539,8 +460,8 @@ int zn_patch_check_batch_dev(const zn_patch_check_item* items, size_t count, uns
     uint64_t wg = 0;
     for (size_t i = 0; i < count; i++) {
       const zn_patch_check_item& it = items[i];
-      if (!patch_elem_ok(it.n, it.elem)) return ZN_E_ARG;
-      if (!it.d_patch || (((uintptr_t)it.d_patch) & 15u) != 0 || it.patch_len < 32u) return ZN_E_ARG;
+      if (!zn_patch_elem_ok(it.n, it.elem)) return ZN_E_ARG;
+      if (!zn_patch_input_ok(it.d_patch, it.patch_len)) return ZN_E_ARG;
       const uint64_t nb = zn_patch_blocks(it.n / (size_t)it.elem);
       segs[i] = ZnPatchCSeg{(const uint8_t*)it.d_patch, it.patch_len, it.n, (uint32_t)wg, (uint32_t)it.elem, (uint32_t)i, 0u};
       wg += nb ? nb : 1u;                        // (a tensor without elements still has a header and first[0])
@@ -563,7 +484,7 @@ int zn_patch_check_batch_dev(const zn_patch_check_item* items, size_t count, uns
     if (table) {
       ZN_HIP(hipEventSynchronize(w.busy));       // the previous batched call may still be reading the pinned staging
       if ((rc = w.h_segs.reserve(table_bytes))) return rc;
-      if ((rc = patch_stage(w, segs, 0, stream))) return rc;
+      if ((rc = zn_patch_stage(w, segs.data(), table_bytes, 0, stream))) return rc;
     }
     zn_launch_patch_check(segs[0], table ? (const ZnPatchCSeg*)w.buf[WS_SEGS] : nullptr, (uint32_t)count, (uint32_t)wg, d_words, stream);
     if (launch_failed()) return ZN_E_HIP;

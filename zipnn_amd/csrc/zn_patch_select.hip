@@ -5,7 +5,7 @@
 // builds from the sliced tensors.
 //
 //   zn_k_patch_select_count / zn_k_patch_place_count   one workgroup per OUTPUT block of 65 536 elements: how many entries it keeps (one word per block)
-//   zn_k_patch_scan                                     (zn_patch.hip, as it is) the block counts become first[], the item's T goes to its total
+//   zn_k_patch_scan                                     (zn_patch.hip) the block counts become first[], the item's T goes to its total
 //   zn_k_patch_select_emit / zn_k_patch_place_emit     one workgroup per output block again: off / val of the kept entries at first[ob] + rank; block 0 writes the header
 //
 // All four are ONE body (zn_ps_block<E, PLACE, EMIT>).  An output block's elements lie in a range of input indices — SELECT: [phi(j_lo), phi(j_hi - 1)], about
@@ -18,22 +18,12 @@
 // PLACE visits every input block from some workgroup, so a place that returns ZN_OK has validated its input whole; SELECT validates the header and the input
 // blocks that overlap the rectangle's rows — the rest is zn_patch_check_batch_dev's job.  The emit instances never write outside [first[ob], first[ob + 1]) of
 // off / val: if the input changed between the two passes the result is wrong, not the memory around it.
-#include "zn_workspace.hpp"
-
-#include <vector>
-
-#define ZN_PS_THREADS 256u
-#define ZN_PS_WAVES (ZN_PS_THREADS / 64u)
-
-template <uint32_t E> struct ZnPsElem;
-template <> struct ZnPsElem<1> { typedef uint8_t t; };
-template <> struct ZnPsElem<2> { typedef uint16_t t; };
-template <> struct ZnPsElem<4> { typedef uint32_t t; };
+#include "zn_patch_host.hpp"
 
 struct ZnPsLds {
-  uint32_t f0[ZN_PS_THREADS], f1[ZN_PS_THREADS];   // the first[] pairs of the 256 input blocks being looked at
-  unsigned long long some[ZN_PS_WAVES];            // … which of them have entries, one mask per wave
-  uint32_t part[2][ZN_PS_WAVES];
+  uint32_t f0[ZN_PATCH_THREADS], f1[ZN_PATCH_THREADS];   // the first[] pairs of the 256 input blocks being looked at
+  unsigned long long some[ZN_PATCH_WAVES];            // … which of them have entries, one mask per wave
+  uint32_t part[2][ZN_PATCH_WAVES];
   uint32_t wrong;
 };
 
@@ -50,18 +40,15 @@ __device__ __forceinline__ uint64_t zn_ps_lower(const ZnPatchSSeg& sg, uint64_t 
 // Output block ob of one item.  !EMIT: words[ob] = the entries it keeps.  EMIT: words[] is first[] of the result; the block's entries go to its off / val.
 template <uint32_t E, bool PLACE, bool EMIT>
 __device__ __forceinline__ void zn_ps_block(const ZnPatchSSeg& sg, uint32_t ob, uint32_t* __restrict__ words, uint32_t* __restrict__ status, ZnPsLds& s) {
-  typedef typename ZnPsElem<E>::t T;
+  typedef typename ZnPatchElem<E>::t T;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint32_t C = sg.C, w = sg.c1 - sg.c0;
   const uint64_t m_all = (uint64_t)sg.R * C, m_rect = (uint64_t)(sg.r1 - sg.r0) * w;
   const uint64_t m_in = PLACE ? m_rect : m_all, m_out = PLACE ? m_all : m_rect;     // (the host has checked: a non-empty rectangle inside the tensor, m_all < 2^32)
   const uint64_t nb_in = zn_patch_blocks(m_in), nb_out = zn_patch_blocks(m_out);
   const uint8_t* p = ZN_GLOBAL_PTR(const uint8_t, sg.in);
-  // the header must describe the item's input, and its L — the formula's value for its T — must be the length we were given: every index below T then lies inside
-  const uint32_t magic = *(const uint32_t*)p, e = *(const uint32_t*)(p + 4);
-  const uint64_t hn = *(const uint64_t*)(p + 8), total = *(const uint64_t*)(p + 16), L = *(const uint64_t*)(p + 24);
-  bool bad = magic != ZN_PATCH_MAGIC || e != E || hn != m_in * E || total > m_in || L != sg.in_len;
-  if (!bad) bad = zn_patch_total(m_in, E, total) != L;
+  uint64_t total;
+  bool bad = !zn_patch_header_ok<E>(zn_patch_header(p), m_in * E, m_in, sg.in_len, total);
   if (bad) {                                     // (workgroup-uniform) nothing behind a wrong header is read
     if (tid == 0) { atomicOr(status, ZN_DEV_CORRUPT); if (!EMIT) words[ob] = 0u; }
     return;
@@ -80,21 +67,10 @@ __device__ __forceinline__ void zn_ps_block(const ZnPatchSSeg& sg, uint32_t ob, 
   if (EMIT) {
     const uint64_t tout = words[nb_out];
     uint8_t* q = ZN_GLOBAL_PTR(uint8_t, sg.out);
-    const uint64_t a1 = zn_patch_a1(nb_out), a2 = zn_patch_a2(nb_out, tout);
     lo = words[ob]; hi = words[ob + 1u];
-    if (tid == 0) {
-      uint32_t* first = (uint32_t*)(q + 32);
-      first[ob] = lo;
-      if ((uint64_t)ob + 1u == nb_out) first[nb_out] = (uint32_t)tout;
-      if (ob == 0) {                             // the header, and the zero padding in front of off[] and of val[]
-        *(uint32_t*)q = ZN_PATCH_MAGIC; *(uint32_t*)(q + 4) = E;
-        *(uint64_t*)(q + 8) = m_out * E; *(uint64_t*)(q + 16) = tout; *(uint64_t*)(q + 24) = a2 + (uint64_t)E * tout;
-        for (uint64_t i = 32u + 4u * (nb_out + 1u); i < a1; i++) q[i] = 0;
-        for (uint64_t i = a1 + 2u * tout; i < a2; i++) q[i] = 0;
-      }
-    }
+    if (tid == 0) zn_patch_emit_head<E>(q, m_out, nb_out, tout, ob, lo);
     if (hi <= lo) return;                        // (workgroup-uniform) this block keeps nothing
-    off_out = (uint16_t*)(q + a1); val_out = (T*)(q + a2);
+    off_out = (uint16_t*)(q + zn_patch_a1(nb_out)); val_out = (T*)(q + zn_patch_a2(nb_out, tout));
   }
   if (in_hi <= in_lo) {                          // (workgroup-uniform; PLACE) no element of the rectangle lies in this block
     if (!EMIT && tid == 0) words[ob] = 0u;
@@ -106,7 +82,7 @@ __device__ __forceinline__ void zn_ps_block(const ZnPatchSSeg& sg, uint32_t ob, 
   const uint32_t ib_lo = (uint32_t)(in_lo / ZN_PATCH_BLOCK), ib_hi = (uint32_t)((in_hi - 1u) / ZN_PATCH_BLOCK);      // (in_hi <= m_in: ib_hi < nb_in)
   if (tid == 0) s.wrong = 0u;
   uint32_t run = 0, step = 0;                    // count: this wave's kept entries; emit: the block's entries in front of this step
-  for (uint32_t ib0 = ib_lo; ib0 <= ib_hi; ib0 += ZN_PS_THREADS) {
+  for (uint32_t ib0 = ib_lo; ib0 <= ib_hi; ib0 += ZN_PATCH_THREADS) {
     // the first[] pairs of up to 256 input blocks, one per thread
     const uint32_t ib = ib0 + tid;
     uint32_t f0 = 0, f1 = 0;
@@ -114,20 +90,20 @@ __device__ __forceinline__ void zn_ps_block(const ZnPatchSSeg& sg, uint32_t ob, 
       f0 = first[ib]; f1 = first[ib + 1u];
       const uint64_t blk0 = (uint64_t)ib * ZN_PATCH_BLOCK;
       const uint64_t left = m_in - blk0 >= (uint64_t)ZN_PATCH_BLOCK ? ZN_PATCH_BLOCK : m_in - blk0;
-      if (f0 > f1 || (uint64_t)f1 > total || (ib == 0 && f0 != 0u) || ((uint64_t)ib + 1u == nb_in && (uint64_t)f1 != total) || (uint64_t)(f1 - f0) > left) { bad = true; f0 = f1 = 0; }
+      if (zn_patch_pair_bad(f0, f1, total, ib, nb_in) || (uint64_t)(f1 - f0) > left) { bad = true; f0 = f1 = 0; }      // (more entries than elements cannot ascend)
     }
     s.f0[tid] = f0; s.f1[tid] = f1;
     const unsigned long long some = __ballot(f1 > f0);
     if (lane == 0) s.some[wave] = some;
     __syncthreads();
-    for (uint32_t wv = 0; wv < ZN_PS_WAVES; wv++) {
+    for (uint32_t wv = 0; wv < ZN_PATCH_WAVES; wv++) {
       unsigned long long mask = s.some[wv];      // (workgroup-uniform: every thread walks the same blocks in the same order)
       while (mask) {
         const uint32_t k = wv * 64u + (uint32_t)__ffsll(mask) - 1u;
         mask &= mask - 1ull;
         const uint32_t g0 = s.f0[k], g1 = s.f1[k];
         const uint64_t blk0 = (uint64_t)(ib0 + k) * ZN_PATCH_BLOCK;
-        for (uint64_t i0 = g0; i0 < g1; i0 += ZN_PS_THREADS) {      // (64 bits: g1 may lie within 256 of 2^32)
+        for (uint64_t i0 = g0; i0 < g1; i0 += ZN_PATCH_THREADS) {      // (64 bits: g1 may lie within 256 of 2^32)
           const uint64_t i = i0 + tid;
           bool keep = false;
           uint32_t oo = 0; T v = (T)0;
@@ -135,7 +111,7 @@ __device__ __forceinline__ void zn_ps_block(const ZnPatchSSeg& sg, uint32_t ob, 
             const uint32_t o = off[i];
             v = val[i];
             const uint64_t x = blk0 + o;         // the entry's index in the input's numbering
-            if (x >= m_in || v == (T)0 || (i > g0 && (uint32_t)off[i - 1u] >= o)) bad = true;
+            if (zn_patch_entry_bad(off, i, g0, o, v, x, m_in)) bad = true;
             else if (PLACE) {
               if (x >= in_lo && x < in_hi) {
                 const uint32_t rr = (uint32_t)x / w, cc = (uint32_t)x - rr * w;
@@ -154,9 +130,8 @@ __device__ __forceinline__ void zn_ps_block(const ZnPatchSSeg& sg, uint32_t ob, 
           if (!EMIT) { run += (uint32_t)__popcll(kept); continue; }
           if (lane == 0) s.part[step & 1u][wave] = (uint32_t)__popcll(kept);      // (two sets of slots: one barrier per step is enough)
           __syncthreads();
-          uint32_t before = 0, all = 0;
-#pragma unroll
-          for (uint32_t q = 0; q < ZN_PS_WAVES; q++) { const uint32_t c = s.part[step & 1u][q]; if (q < wave) before += c; all += c; }
+          uint32_t before, all;
+          zn_patch_wave_sums(s.part[step & 1u], wave, before, all);
           if (keep) {
             const uint32_t pos = lo + run + before + (uint32_t)__popcll(kept & ((1ull << lane) - 1ull));
             if (pos < hi) { off_out[pos] = (uint16_t)oo; val_out[pos] = v; }      // never outside the block's own range, whatever the input holds by now
@@ -174,21 +149,14 @@ __device__ __forceinline__ void zn_ps_block(const ZnPatchSSeg& sg, uint32_t ob, 
   if (tid == 0) {
     const bool wrong = s.wrong != 0u;
     if (wrong) atomicOr(status, ZN_DEV_CORRUPT);
-    if (!EMIT) { uint32_t c = 0; for (uint32_t q = 0; q < ZN_PS_WAVES; q++) c += s.part[0][q]; words[ob] = wrong ? 0u : c; }
+    if (!EMIT) { uint32_t c = 0; for (uint32_t q = 0; q < ZN_PATCH_WAVES; q++) c += s.part[0][q]; words[ob] = wrong ? 0u : c; }
   }
-}
-
-__device__ __forceinline__ ZnPatchSSeg zn_ps_find(const ZnPatchSSeg& one, const ZnPatchSSeg* __restrict__ segs, uint32_t nseg, uint32_t b) {
-  if (segs == nullptr) return one;
-  uint32_t lo = 0, hi = nseg;
-  while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (segs[mid].wg0 <= b) lo = mid; else hi = mid; }
-  return segs[lo];
 }
 
 template <bool PLACE, bool EMIT>
 __device__ __forceinline__ void zn_ps_dispatch(const ZnPatchSSeg& one, const ZnPatchSSeg* __restrict__ segs_, uint32_t nseg, uint32_t* words_, uint32_t* status_, ZnPsLds& s) {
   const ZnPatchSSeg* segs = ZN_GLOBAL_PTR(const ZnPatchSSeg, segs_);
-  const ZnPatchSSeg sg = zn_ps_find(one, segs, nseg, blockIdx.x);
+  const ZnPatchSSeg sg = zn_patch_find(one, segs, nseg, blockIdx.x);
   uint32_t* words = ZN_GLOBAL_PTR(uint32_t, words_) + sg.w0;
   uint32_t* status = ZN_GLOBAL_PTR(uint32_t, status_);
   const uint32_t ob = blockIdx.x - sg.wg0;
@@ -198,7 +166,7 @@ __device__ __forceinline__ void zn_ps_dispatch(const ZnPatchSSeg& one, const ZnP
 }
 
 #define ZN_PS_KERNEL(NAME, PLACE, EMIT)                                                                                                                          \
-  __global__ void __launch_bounds__(ZN_PS_THREADS) NAME(const ZnPatchSSeg one, const ZnPatchSSeg* __restrict__ segs, uint32_t nseg, uint32_t* __restrict__ words, \
+  __global__ void __launch_bounds__(ZN_PATCH_THREADS) NAME(const ZnPatchSSeg one, const ZnPatchSSeg* __restrict__ segs, uint32_t nseg, uint32_t* __restrict__ words, \
                                                         uint32_t* __restrict__ status) {                                                                         \
     __shared__ ZnPsLds s;                                                                                                                                        \
     zn_ps_dispatch<PLACE, EMIT>(one, segs, nseg, words, status, s);                                                                                              \
@@ -211,108 +179,49 @@ ZN_PS_KERNEL(zn_k_patch_place_emit, true, true)
 
 void zn_launch_patch_select_count(bool place, const ZnPatchSSeg& one, const ZnPatchSSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_words, uint32_t* d_status, hipStream_t stream) {
   if (nseg == 0 || total_wg == 0) return;
-  if (place) hipLaunchKernelGGL(zn_k_patch_place_count, dim3(total_wg), dim3(ZN_PS_THREADS), 0, stream, one, d_segs, nseg, d_words, d_status);
-  else hipLaunchKernelGGL(zn_k_patch_select_count, dim3(total_wg), dim3(ZN_PS_THREADS), 0, stream, one, d_segs, nseg, d_words, d_status);
+  if (place) hipLaunchKernelGGL(zn_k_patch_place_count, dim3(total_wg), dim3(ZN_PATCH_THREADS), 0, stream, one, d_segs, nseg, d_words, d_status);
+  else hipLaunchKernelGGL(zn_k_patch_select_count, dim3(total_wg), dim3(ZN_PATCH_THREADS), 0, stream, one, d_segs, nseg, d_words, d_status);
   zn_note_kernel(place ? "zn_k_patch_place_count" : "zn_k_patch_select_count");
 }
 void zn_launch_patch_select_emit(bool place, const ZnPatchSSeg& one, const ZnPatchSSeg* d_segs, uint32_t nseg, uint32_t total_wg, const uint32_t* d_words, uint32_t* d_status, hipStream_t stream) {
   if (nseg == 0 || total_wg == 0) return;
-  if (place) hipLaunchKernelGGL(zn_k_patch_place_emit, dim3(total_wg), dim3(ZN_PS_THREADS), 0, stream, one, d_segs, nseg, const_cast<uint32_t*>(d_words), d_status);
-  else hipLaunchKernelGGL(zn_k_patch_select_emit, dim3(total_wg), dim3(ZN_PS_THREADS), 0, stream, one, d_segs, nseg, const_cast<uint32_t*>(d_words), d_status);
+  if (place) hipLaunchKernelGGL(zn_k_patch_place_emit, dim3(total_wg), dim3(ZN_PATCH_THREADS), 0, stream, one, d_segs, nseg, const_cast<uint32_t*>(d_words), d_status);
+  else hipLaunchKernelGGL(zn_k_patch_select_emit, dim3(total_wg), dim3(ZN_PATCH_THREADS), 0, stream, one, d_segs, nseg, const_cast<uint32_t*>(d_words), d_status);
   zn_note_kernel(place ? "zn_k_patch_place_emit" : "zn_k_patch_select_emit");
 }
 
 // ---- the C ABI of select and place (host side: checks, tables, launches) ----
 namespace {
 
-bool select_overlap(const void* p, size_t pn, const void* q, size_t qn) { return (uintptr_t)p < (uintptr_t)q + qn && (uintptr_t)q < (uintptr_t)p + pn; }
-
-// `bytes` of a table through the pinned staging buffer into WS_SEGS at byte offset `at`; the caller has synchronised with the buffer's last reader
-int select_stage(Workspace& w, const void* table, size_t bytes, size_t at, hipStream_t stream) {
-  memcpy((uint8_t*)w.h_segs.p + at, table, bytes);
-  ZN_HIP(hipMemcpyAsync((uint8_t*)w.buf[WS_SEGS] + at, (uint8_t*)w.h_segs.p + at, bytes, hipMemcpyHostToDevice, stream));
-  return ZN_OK;
-}
-
-// Count, scan, one read-back of every item's T and of the verdict; with `emit`: capacity check, then the emit pass for the items that keep entries.  Synchronous.
+// The sizes of the selected / placed patches; with `emit`: … and the patches, where every capacity suffices (zn_patch_two_pass).  Every item has at least one
+// output block: the rectangle is not empty; lens[i] == 0: no entry results.
 int patch_select(const zn_patch_select_item* items, size_t count, std::vector<uint64_t>& lens, bool place, bool emit, hipStream_t stream) {
   lens.assign(count, 0);
   if (count == 0) return ZN_OK;
   if (count > 0x7FFFFFFFull) return ZN_E_ARG;
   std::vector<ZnPatchSSeg> segs(count);
-  std::vector<ZnPatchBSeg> scan(count);          // the scan kernel's view of the same items: the OUTPUT's m, and w0
-  std::vector<uint64_t> m_out(count);
+  std::vector<ZnPatchBSeg> scan(count);
+  std::vector<size_t> caps(count);
   uint64_t wg = 0, words = 0;
   for (size_t i = 0; i < count; i++) {
     const zn_patch_select_item& it = items[i];
-    if (it.elem != 1 && it.elem != 2 && it.elem != 4) return ZN_E_ARG;
-    if (it.rows == 0 || it.cols == 0 || it.rows >= (1ull << 32) || it.cols >= (1ull << 32) || (uint64_t)it.rows * (uint64_t)it.cols >= (1ull << 32)) return ZN_E_ARG;
+    if (it.rows == 0 || it.cols == 0 || it.rows >= (1ull << 32) || it.cols >= (1ull << 32) || !zn_patch_count_ok(it.elem, (uint64_t)it.rows * (uint64_t)it.cols)) return ZN_E_ARG;
     if (it.row_lo >= it.row_hi || it.row_hi > it.rows || it.col_lo >= it.col_hi || it.col_hi > it.cols) return ZN_E_ARG;
-    if (!it.d_patch || (((uintptr_t)it.d_patch) & 15u) != 0 || it.patch_len < 32u) return ZN_E_ARG;
-    if (emit && it.out_cap) {
-      if (!it.d_out || (((uintptr_t)it.d_out) & 15u) != 0) return ZN_E_ARG;
-      if (select_overlap(it.d_out, it.out_cap, it.d_patch, it.patch_len)) return ZN_E_ARG;
-    }
+    if (!zn_patch_input_ok(it.d_patch, it.patch_len)) return ZN_E_ARG;
+    if (emit && it.out_cap && (!zn_patch_out_ok(it.d_out) || zn_patch_overlap(it.d_out, it.out_cap, it.d_patch, it.patch_len))) return ZN_E_ARG;
     const uint64_t m_all = (uint64_t)it.rows * it.cols, m_rect = (uint64_t)(it.row_hi - it.row_lo) * (it.col_hi - it.col_lo);
-    m_out[i] = place ? m_all : m_rect;
-    const uint64_t nb = zn_patch_blocks(m_out[i]);                               // (>= 1: the rectangle is not empty)
+    const uint64_t m_out = place ? m_all : m_rect, nb = zn_patch_blocks(m_out);
     segs[i] = ZnPatchSSeg{(const uint8_t*)it.d_patch, it.patch_len, (uint8_t*)it.d_out, (uint32_t)it.rows, (uint32_t)it.cols, (uint32_t)it.row_lo, (uint32_t)it.row_hi,
                           (uint32_t)it.col_lo, (uint32_t)it.col_hi, (uint32_t)wg, (uint32_t)words, (uint32_t)it.elem, 0u};
-    scan[i] = ZnPatchBSeg{nullptr, nullptr, nullptr, m_out[i], 0u, (uint32_t)words, (uint32_t)it.elem, 0u};
+    scan[i] = ZnPatchBSeg{nullptr, nullptr, nullptr, m_out, 0u, (uint32_t)words, (uint32_t)it.elem, 0u};
+    caps[i] = it.out_cap;
     wg += nb;
     words += nb + 1u;
     if (wg > 0x7FFFFFFFull || words > 0x7FFFFFFFull) return ZN_E_ARG;
   }
-  WsLease L;
-  if (L.rc) return L.rc;
-  Workspace& w = *L.w;
-  t_kernels.clear();
-  int rc;
-  const bool table = count > 1;
-  const size_t sseg_bytes = table ? count * sizeof(ZnPatchSSeg) : 0u, bseg_bytes = table ? count * sizeof(ZnPatchBSeg) : 0u;
-  const size_t table_bytes = 2u * sseg_bytes + bseg_bytes;                       // count table, scan table, emit table (the emit pass has a grid of its own)
-  const size_t back_bytes = (count + 1u) * sizeof(uint64_t);                     // every item's T, and the verdict word behind them
-  if ((rc = w.reserve(WS_META_A, words * sizeof(uint32_t)))) return rc;
-  if ((rc = w.reserve(WS_TOTALS, back_bytes))) return rc;
-  if ((rc = w.h_totals.reserve(back_bytes))) return rc;
-  if (table && (rc = w.reserve(WS_SEGS, table_bytes))) return rc;
-  if ((rc = L.acquire(stream))) return rc;
-  L.mark = table;
-  uint32_t* d_words = (uint32_t*)w.buf[WS_META_A];
-  uint64_t* d_totals = (uint64_t*)w.buf[WS_TOTALS];
-  uint32_t* d_status = (uint32_t*)(d_totals + count);
-  ZN_HIP(hipMemsetAsync(d_status, 0, sizeof(uint64_t), stream));
-  if (table) {
-    ZN_HIP(hipEventSynchronize(w.busy));         // the previous batched call may still be reading the pinned staging
-    if ((rc = w.h_segs.reserve(table_bytes))) return rc;
-    if ((rc = select_stage(w, segs.data(), sseg_bytes, 0, stream))) return rc;
-    if ((rc = select_stage(w, scan.data(), bseg_bytes, sseg_bytes, stream))) return rc;
-  }
-  const uint8_t* d_tab = (const uint8_t*)w.buf[WS_SEGS];
-  zn_launch_patch_select_count(place, segs[0], table ? (const ZnPatchSSeg*)d_tab : nullptr, (uint32_t)count, (uint32_t)wg, d_words, d_status, stream);
-  zn_launch_patch_scan(scan[0], table ? (const ZnPatchBSeg*)(d_tab + sseg_bytes) : nullptr, (uint32_t)count, d_words, d_totals, stream);
-  if (launch_failed()) return ZN_E_HIP;
-  ZN_HIP(hipMemcpyAsync(w.h_totals.p, d_totals, back_bytes, hipMemcpyDeviceToHost, stream));
-  ZN_HIP(hipStreamSynchronize(stream));
-  const uint64_t* T = (const uint64_t*)w.h_totals.p;
-  if ((uint32_t)T[count] & ZN_DEV_CORRUPT) return ZN_E_CORRUPT;
-  bool short_cap = false;
-  for (size_t i = 0; i < count; i++) {
-    lens[i] = T[i] ? zn_patch_total(m_out[i], segs[i].E, T[i]) : 0u;            // (0: no entry results)
-    if (emit && lens[i] > items[i].out_cap) short_cap = true;
-  }
-  if (!emit) return ZN_OK;
-  if (short_cap) return ZN_E_CAP;
-  uint64_t ewg = 0;
-  for (size_t i = 0; i < count; i++) { segs[i].wg0 = (uint32_t)ewg; if (T[i]) ewg += zn_patch_blocks(m_out[i]); }
-  if (ewg == 0) return ZN_OK;
-  // (the first tables' copies are over — the stream was synchronised —; the emit table goes behind them)
-  if (table && (rc = select_stage(w, segs.data(), sseg_bytes, sseg_bytes + bseg_bytes, stream))) return rc;
-  zn_launch_patch_select_emit(place, segs[0], table ? (const ZnPatchSSeg*)(d_tab + sseg_bytes + bseg_bytes) : nullptr, (uint32_t)count, (uint32_t)ewg, d_words, d_status, stream);
-  if (launch_failed()) return ZN_E_HIP;
-  ZN_HIP(hipMemcpyAsync(w.h_totals.p, d_status, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));      // an input that changed under the call
-  ZN_HIP(hipStreamSynchronize(stream));
-  return ((uint32_t)T[0] & ZN_DEV_CORRUPT) ? ZN_E_CORRUPT : ZN_OK;
+  return zn_patch_two_pass(segs, scan.data(), wg, words, emit ? caps.data() : nullptr, lens, stream,
+                           [place](const ZnPatchSSeg& one, const ZnPatchSSeg* d, uint32_t n, uint32_t g, uint32_t* wd, uint32_t* st, hipStream_t q) { zn_launch_patch_select_count(place, one, d, n, g, wd, st, q); },
+                           [place](const ZnPatchSSeg& one, const ZnPatchSSeg* d, uint32_t n, uint32_t g, uint32_t* wd, uint32_t* st, hipStream_t q) { zn_launch_patch_select_emit(place, one, d, n, g, wd, st, q); });
 }
 
 int select_sizes(const zn_patch_select_item* items, size_t count, size_t* sizes_out, bool place, void* stream_) {
