@@ -337,7 +337,22 @@ int zn_digest_host(const void* src, size_t n, unsigned long long* out);
  *   entries_out[i] (host, may be NULL) = T of a well-formed item, 0 otherwise.  The call returns ZN_OK whenever it ran — the verdicts are per item —, ZN_E_ARG before
  *   any launch for patch_len < 32, a d_patch that is null or not 16-byte aligned, or an (n, elem) that is not eligible.
  *   What it cannot see: a first[] boundary moved so that both neighbouring blocks still ascend is a well-formed patch — of another tensor.  Only the content
- *   digests (verify) catch that. */
+ *   digests (verify) catch that.
+ * zn_patch_apply_strided_batch_dev: the patch applied through a STRIDED VIEW of live memory whose logical row-major order is the tensor's: a
+ *   weight kept transposed, a column slice of a fused buffer, a tile-shuffled or channels-last layout.  An index map per entry, not a pass over the tensor.
+ *   d_dst (elem-aligned) is where LOGICAL element 0 lies; size[] / stride[] (strides in ELEMENTS, ndim in 0 .. ZN_PATCH_MAX_DIMS, ndim == 0: one element)
+ *   describe the view, and the sizes' product must be n / elem.  The call is IN PLACE ONLY: no d_base, no byte window, no plan form — the whole patch is
+ *   always applied, every block is visited, and a call that returns clean has validated everything but the canonical padding.  One launch for the batch
+ *   (zn_k_patch_apply_strided: one workgroup per block of every item); the verdict goes through the call's status slot — check, zn_decode_status,
+ *   zn_decode_status_chain — exactly as zn_patch_apply_batch_dev's, with the same tests; an entry that fails them is not applied.  Nothing outside
+ *   [d_patch, d_patch + patch_len) is read, and nothing is written but the elem bytes of elements of the view.
+ *   Before the launch the host makes the layout canonical — dimensions of size 1 dropped, neighbours merged where stride[i] == size[i + 1] stride[i + 1]; a
+ *   batch whose layouts all collapse to contiguous tensors takes zn_patch_apply_batch_dev's launch — and tests what remains for INJECTIVITY: sorted by stride
+ *   ascending, every stride must exceed the sum over the smaller ones of (size - 1) stride, and no stride is 0.  The test is SUFFICIENT, NOT NECESSARY: it
+ *   refuses expand() and overlapping as_strided views, and also injective views whose dimensions interleave.  ZN_E_ARG before any launch: ndim outside
+ *   0 .. ZN_PATCH_MAX_DIMS, a product of the sizes that is not n / elem, a negative stride, a layout that fails the test or whose last element lies 2^62
+ *   elements or more from the first, an (n, elem) that is not eligible, d_dst null with n > 0 or not elem-aligned, d_patch null or not 16-byte aligned,
+ *   patch_len < 32.  A patch with T == 0 and a tensor with n == 0 are valid and write nothing. */
 #define ZN_PATCH_BAD_HEADER 1u
 #define ZN_PATCH_BAD_FIRST 2u
 #define ZN_PATCH_BAD_OFFSET 4u
@@ -363,6 +378,14 @@ int zn_patch_apply_batch_dev(const zn_patch_apply_item* items, size_t count, voi
 int zn_patch_plan_create(const zn_patch_apply_item* items, size_t count, zn_patch_plan** plan);
 int zn_patch_plan_run(zn_patch_plan* plan, void* stream, int check);
 int zn_patch_plan_destroy(zn_patch_plan* plan);
+#define ZN_PATCH_MAX_DIMS 8
+typedef struct zn_patch_apply_strided_item {
+  const void* d_patch; size_t patch_len;    /* 16-byte aligned, >= 32 */
+  size_t n; int elem;                       /* the whole tensor: n bytes, elements of elem */
+  void* d_dst;                              /* where LOGICAL element 0 lies; elem-aligned */
+  int ndim; unsigned long long size[ZN_PATCH_MAX_DIMS]; long long stride[ZN_PATCH_MAX_DIMS];   /* strides in elements */
+} zn_patch_apply_strided_item;
+int zn_patch_apply_strided_batch_dev(const zn_patch_apply_strided_item* items, size_t count, void* stream, int check);
 typedef struct zn_patch_check_item { const void* d_patch; size_t patch_len; size_t n; int elem; } zn_patch_check_item;
 int zn_patch_check_batch_dev(const zn_patch_check_item* items, size_t count,
                              unsigned int* verdicts_out,        /* host, one per item: 0 = well-formed */

@@ -47,6 +47,10 @@ blocks of leg b as the base, the two fine-tunes of --delta:
   h  one rank of a split of 8 of a 2 % fine-tune over a resident indexed base (q/k/v/gate/up along dim 0, o/down along dim 1), every comparison interleaved in
      both orders (A B A B B A B A: the four A runs are the A/A spread): sharded against get_tensors + narrow + from_state_dict; the select call against the build
      call on the same shard pairs, dim 0 and dim 1 apart; plan.run of one block from the sharded store against a store built from the shard tensors
+--strided: apply_ / revert_ on non-contiguous live tensors instead (zn_patch_apply_strided_batch_dev), into profiles/resident_strided.{json,txt}:
+  t  apply_ + revert_ of one block of a 2 % fine-tune kept sparse over a resident indexed base, on contiguous targets, transposed storage, dim-1 narrows of a
+     twice-as-wide buffer and a 16-row tile shuffle; each strided layout against contiguous() + the contiguous apply + copy_ back, interleaved with the
+     contiguous run in both orders (C S W C S W W S C W S C: the contiguous runs are the A/A spread)
 """
 import argparse
 import json
@@ -1124,6 +1128,116 @@ def main_sparse_file(args):
     return 0
 
 
+def leg_t(args):
+    """--strided: apply_ + revert_ of one Llama-3-8B block from a sparse variant over a resident indexed base, on live tensors in four layouts:
+    contiguous; transposed storage; dim-1 narrows of a twice-as-wide buffer; a 16-row tile shuffle (view(R/16, 16, C/32, 32).permute(0, 2, 1, 3).contiguous(), patched
+    through the inverse 4-D view by one zn_patch_apply_strided_batch_dev call per direction, since the view has another shape than the entry).  Each strided layout
+    against the workaround that exists without the strided call — contiguous() + the contiguous apply + copy_ back —, interleaved with the contiguous run in both orders."""
+    import torch
+    from zipnn_amd import ResidentCheckpoint, _capi, codec
+    lib = _capi.lib()
+    sd, per = _blocks(args.layers)
+    names = per[0]
+    base = ResidentCheckpoint.from_state_dict(sd, "cuda:0", index=True)
+    ft = _fine_tune(sd, "sparse", 21)
+    store = ResidentCheckpoint.from_state_dict(ft, "cuda:0", base=base, sparse=True)
+    st = torch.cuda.current_stream().cuda_stream
+    two_d = [k for k in names if sd[k].dim() == 2]
+    assert all(store.info(k)["delta"] == "sparse" for k in two_d)
+
+    def live_of(layout):
+        """-> {name: live view holding the base's values} (1-D tensors stay contiguous)"""
+        out = {}
+        for k in names:
+            w = sd[k]
+            if layout == "contiguous" or w.dim() != 2:
+                out[k] = w.clone()
+            elif layout == "transposed":
+                out[k] = w.t().contiguous().t()
+            elif layout == "narrow":
+                fused = torch.zeros(w.shape[0], 2 * w.shape[1], dtype=w.dtype, device=w.device)
+                out[k] = fused[:, w.shape[1] // 2: w.shape[1] // 2 + w.shape[1]]
+                out[k].copy_(w)
+            else:                                             # "tile": the 4-D view whose row-major order is the tensor's, over tile-shuffled storage
+                R, C = w.shape
+                out[k] = w.view(R // 16, 16, C // 32, 32).permute(0, 2, 1, 3).contiguous().permute(0, 2, 1, 3)
+        return out
+
+    def runner(layout, live):
+        if layout != "tile":
+            return lambda: (store.apply_(live, check=False), store.revert_(live, check=False))
+        items = [codec.patch_strided_item(live[k], store.patch(k)) for k in two_d]
+        rest = {k: live[k] for k in names if k not in two_d}
+        return lambda: (store.apply_(rest, check=False), lib.patch_apply_strided_batch_dev(items, st, False), store.revert_(rest, check=False), lib.patch_apply_strided_batch_dev(items, st, False))
+
+    def workaround(live):
+        def once(call):
+            tmp = {k: live[k].contiguous().view(sd[k].shape) for k in names}
+            call(tmp, check=False)
+            for k in two_d:
+                live[k].copy_(tmp[k].view(live[k].shape))
+        return lambda: (once(store.apply_), once(store.revert_))
+
+    def holds(live, want):
+        return all(_same(live[k].contiguous(), want[k]) for k in names)
+
+    res = {"layers": args.layers, "block_bytes": sum(sd[k].numel() * 2 for k in names), "patch_bytes": sum(store.patch(k).numel() for k in two_d), "tensors": len(names), "layouts": []}
+    contig = live_of("contiguous")
+    run_c = runner("contiguous", contig)
+    for layout in ("transposed", "narrow", "tile"):
+        live_s, live_w = live_of(layout), live_of(layout)
+        fns = {"contiguous": run_c, "strided": runner(layout, live_s), "workaround": workaround(live_w)}
+        runs, kernels = {k: [] for k in fns}, {}
+        for leg in ("contiguous", "strided", "workaround", "contiguous", "strided", "workaround", "workaround", "strided", "contiguous", "workaround", "strided", "contiguous"):
+            runs[leg].append(_events_ms(fns[leg], args.reps)["median_ms"])
+            store.status()
+            kernels[leg] = _capi_kernels()
+        assert holds(contig, sd) and holds(live_s, sd) and holds(live_w, sd), layout          # every pair left the tensors as it found them
+        if layout == "tile":
+            lib.patch_apply_strided_batch_dev([codec.patch_strided_item(live_s[k], store.patch(k)) for k in two_d], st, True)
+            store.apply_({k: live_s[k] for k in names if k not in two_d})
+        else:
+            store.apply_(live_s)
+        assert holds(live_s, ft), layout
+        res["layouts"].append({"layout": layout, "runs_ms": runs, "kernels": kernels, "median_ms": {k: statistics.median(v) for k, v in runs.items()}})
+        del live_s, live_w, fns
+        torch.cuda.empty_cache()
+    allc = [x for r in res["layouts"] for x in r["runs_ms"]["contiguous"]]
+    res["aa_spread"] = (max(allc) - min(allc)) / min(allc)
+    return res
+
+
+def main_strided(args):
+    p = subprocess.run(["timeout", "-k", "10", "540", sys.executable, os.path.abspath(__file__), "--leg", "t", "--layers", str(args.layers), "--reps", str(args.reps)],
+                       capture_output=True, text=True)
+    line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+    if p.returncode != 0 or not line:
+        print(f"leg t failed (exit {p.returncode})\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}")
+        return 1
+    res = json.loads(line[0][7:])
+    out = args.out if args.out != os.path.join(ROOT, "profiles", "resident_decode") else os.path.join(ROOT, "profiles", "resident_strided")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    lines = [f"command: python scripts/bench_resident.py --strided --layers {args.layers} --reps {args.reps}",
+             f"strided apply probe (ResidentCheckpoint.apply_ / revert_ on non-contiguous live tensors, DESIGN §3.15): one Llama-3-8B block ({res['tensors']} tensors, {res['block_bytes']} B, bf16),",
+             f"a 2 % fine-tune kept sparse ({res['patch_bytes']} B of patches) over a resident indexed base; apply_ + revert_ between device events, median ms of {args.reps} pairs per run;",
+             "per layout the runs are interleaved in both orders (C S W C S W W S C W S C: contiguous targets, the strided call, the workaround contiguous() + contiguous apply + copy_ back);",
+             "after the runs every tensor holds the base's bytes, and the fine-tune's after one more apply",
+             f"A/A spread of the {sum(len(r['runs_ms']['contiguous']) for r in res['layouts'])} contiguous runs: {100 * res['aa_spread']:.1f} %"]
+    for r in res["layouts"]:
+        q, m = r["runs_ms"], r["median_ms"]
+        gain = 1.0 - m["strided"] / m["workaround"]
+        verdict = "beats the workaround by more than the spread" if gain > res["aa_spread"] else "LOSES to the workaround" if gain < -res["aa_spread"] else "inside the spread of the workaround"
+        lines.append(f"  {r['layout']:<11} contiguous " + " / ".join(f"{x:.4f}" for x in q["contiguous"]) + "   strided " + " / ".join(f"{x:.4f}" for x in q["strided"]) +
+                     "   workaround " + " / ".join(f"{x:.4f}" for x in q["workaround"]))
+        lines.append(f"              medians: contiguous {m['contiguous']:.4f}, strided {m['strided']:.4f}, workaround {m['workaround']:.4f}: the strided call takes {m['strided'] / m['workaround']:.2f} of the workaround's time"
+                     f" and {m['strided'] / m['contiguous']:.2f} of the contiguous targets' — {verdict}")
+        lines.append(f"              last call's kernels: strided [{r['kernels']['strided']}]  workaround [{r['kernels']['workaround']}]")
+    open(out + ".txt", "w").write("\n".join(lines) + "\n")
+    json.dump(res, open(out + ".json", "w"), indent=1)
+    print("\n".join(lines))
+    return 0
+
+
 def main_index(args):
     results = {}
     for leg, limit in INDEX_LEG_SECONDS.items():
@@ -1169,6 +1283,7 @@ def main():
     ap.add_argument("--sparse-file", action="store_true", help="the sparse file leg (f) instead of a-e")
     ap.add_argument("--rebase", action="store_true", help="the patch merge / rebased leg (r) instead of a-e")
     ap.add_argument("--shard", action="store_true", help="the patch select / sharded leg (h) instead of a-e")
+    ap.add_argument("--strided", action="store_true", help="the strided apply leg (t) instead of a-e")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resident_decode"))
     args = ap.parse_args()
     if args.leg:                                          # a child: one leg, its result as one JSON line
@@ -1192,6 +1307,8 @@ def main():
         return main_rebase(args)
     if args.shard:
         return main_shard(args)
+    if args.strided:
+        return main_strided(args)
     results = {}
     for leg, limit in LEG_SECONDS.items():
         p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--layers", str(args.layers), "--reps", str(args.reps)],

@@ -100,6 +100,17 @@ class ZnPatchApplyItem(ctypes.Structure):
 
 assert ctypes.sizeof(ZnPatchApplyItem) == 64
 
+PATCH_MAX_DIMS = 8
+
+
+class ZnPatchApplyStridedItem(ctypes.Structure):
+    """struct zn_patch_apply_strided_item of include/zipnn_hip.h"""
+    _fields_ = [("d_patch", ctypes.c_void_p), ("patch_len", ctypes.c_size_t), ("n", ctypes.c_size_t), ("elem", ctypes.c_int), ("d_dst", ctypes.c_void_p),
+                ("ndim", ctypes.c_int), ("size", ctypes.c_ulonglong * PATCH_MAX_DIMS), ("stride", ctypes.c_longlong * PATCH_MAX_DIMS)]
+
+
+assert ctypes.sizeof(ZnPatchApplyStridedItem) == 176
+
 
 class ZnPatchCheckItem(ctypes.Structure):
     """struct zn_patch_check_item of include/zipnn_hip.h"""
@@ -256,6 +267,9 @@ class ZnLib:
             for f in (L.zn_patch_select_batch_dev, L.zn_patch_place_batch_dev):
                 f.restype = ci
                 f.argtypes = [ctypes.POINTER(ZnPatchSelectItem), sz, vp]
+        if hasattr(L, "zn_patch_apply_strided_batch_dev"):      # (likewise: a library from before the strided apply)
+            L.zn_patch_apply_strided_batch_dev.restype = ci
+            L.zn_patch_apply_strided_batch_dev.argtypes = [ctypes.POINTER(ZnPatchApplyStridedItem), sz, vp, ci]
         L.zn_copy_to_host.restype = ci; L.zn_copy_to_host.argtypes = [vp, vp, sz]
         L.zn_release_workspace.restype = ci
         L.zn_set_legacy_tree_descriptions.restype = ci
@@ -670,6 +684,20 @@ class ZnLib:
         window are XORed into dst_ptr (where the window's first byte lies) — in place, or over a copy of the base's window when base_ptr is given."""
         arr, n = self._patch_apply_items(items)
         self._check(self._L.zn_patch_apply_batch_dev(arr, n, ctypes.c_void_p(stream or None), 1 if check else 0))
+
+    def patch_apply_strided_batch_dev(self, items, stream=0, check=True):
+        """zn_patch_apply_strided_batch_dev.  items: iterable of (patch_ptr, patch_len, n, elem, dst_ptr, sizes, strides): the whole patch XORed in place into the
+        strided view whose LOGICAL element 0 lies at dst_ptr (strides in elements).  More than PATCH_MAX_DIMS dimensions reach the library as they are: it refuses them."""
+        items = list(items)
+        arr = (ZnPatchApplyStridedItem * max(len(items), 1))()
+        for i, (pp, pl, n, el, dp, sizes, strides) in enumerate(items):
+            if len(sizes) != len(strides):
+                raise ValueError("patch_apply_strided: one stride per dimension")
+            arr[i].d_patch = pp or None; arr[i].patch_len = pl; arr[i].n = n; arr[i].elem = el; arr[i].d_dst = dp or None
+            arr[i].ndim = len(sizes)
+            for d, (sz_, st_) in enumerate(zip(sizes[:PATCH_MAX_DIMS], strides[:PATCH_MAX_DIMS])):
+                arr[i].size[d] = sz_; arr[i].stride[d] = st_
+        self._check(self._L.zn_patch_apply_strided_batch_dev(arr, len(items), ctypes.c_void_p(stream or None), 1 if check else 0))
 
     def patch_plan_create(self, items):
         """zn_patch_plan_create over items as for patch_apply_batch_dev -> an opaque handle (patch_plan_run / patch_plan_destroy)."""

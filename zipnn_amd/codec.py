@@ -313,21 +313,56 @@ def patch_build(t, base):
     return patch_build_device_batch(_capi.lib(), [(flat_bytes(t.detach()), flat_bytes(base.detach()), el)])[0]
 
 
+def patch_layout_refusal(t):
+    """Why zn_patch_apply_strided_batch_dev would refuse the strided view `t` (include/zipnn_hip.h; the library's own test, restated so that the error can say
+    why), or None: more than 8 dimensions, a stride of 0 (expand()), or dimensions that overlap — sorted by stride, a stride that does not exceed the sum over
+    the smaller ones of (size - 1) stride.  The test is sufficient, not necessary."""
+    from . import _capi
+    if t.dim() > _capi.PATCH_MAX_DIMS:
+        return f"{t.dim()} dimensions (at most {_capi.PATCH_MAX_DIMS})"
+    span = 0
+    for st, sz in sorted((st, sz) for sz, st in zip(t.shape, t.stride()) if sz != 1):
+        if st < 0:
+            return "a negative stride"
+        if st == 0:
+            return "a stride of 0 (an expanded view: several elements share memory)"
+        if st <= span:
+            return f"strides {tuple(t.stride())} over sizes {tuple(t.shape)} may overlap (stride {st} does not step past the {span} elements the smaller strides span)"
+        span += (sz - 1) * st
+    return None
+
+
+def patch_strided_item(t, patch):
+    """-> the item of ZnLib.patch_apply_strided_batch_dev that applies `patch` (a uint8 tensor) through the strided view `t`; ValueError where the view is refused."""
+    why = patch_layout_refusal(t) if t.numel() else None
+    if why:
+        raise ValueError(f"patch: the view cannot be patched in place: {why}")
+    el = t.element_size()
+    return (patch.data_ptr(), patch.numel(), t.numel() * el, el, t.data_ptr() if t.numel() else 0, tuple(t.shape), tuple(t.stride()))
+
+
 def patch_apply_(t, patch, check=True):
     """t ^= patch, in place: a tensor that holds the base's values holds the fine-tune's afterwards, and the base's again after a second call.  patch: what
-    patch_build returned (None: nothing to do).  A malformed patch raises (ZN_E_CORRUPT / ZN_E_ARG) and never writes outside `t`.  -> t"""
+    patch_build returned (None: nothing to do).  `t` may have any shape and strides: only its numel and its LOGICAL row-major order matter — a transposed
+    weight, a column slice of a fused buffer, the N-D view that undoes a tile shuffle.  A contiguous `t` takes zn_patch_apply_batch_dev; any other goes through
+    its layout (zn_patch_apply_strided_batch_dev, DESIGN §3.15: an index map per entry, no pass over the tensor, no scratch copy), provided its strides pass the
+    library's injectivity test — expand()ed and overlapping views raise a ValueError that says why.  A malformed patch raises (ZN_E_CORRUPT / ZN_E_ARG) and
+    never writes outside the elements of `t`.  -> t"""
     from . import _capi
     if patch is None:
         return t
     d = t.detach()
     el = patch_elem(d)
-    if el is None or not d.is_contiguous():
-        raise ValueError("patch_apply_: a contiguous tensor with elements of 1, 2 or 4 bytes")
+    if el is None:
+        raise ValueError("patch_apply_: a tensor with elements of 1, 2 or 4 bytes, fewer than 2^32 of them")
     if patch.dtype != torch.uint8 or patch.device != d.device or not patch.is_contiguous():
         raise ValueError("patch_apply_: the patch is a contiguous uint8 tensor on the tensor's device")
     n = d.numel() * el
     with _device_of(d.device):
-        _capi.lib().patch_apply_batch_dev([(patch.data_ptr(), patch.numel(), n, el, 0, n, d.data_ptr() if n else 0)], _stream_handle(d), check)
+        if d.is_contiguous():
+            _capi.lib().patch_apply_batch_dev([(patch.data_ptr(), patch.numel(), n, el, 0, n, d.data_ptr() if n else 0)], _stream_handle(d), check)
+        else:
+            _capi.lib().patch_apply_strided_batch_dev([patch_strided_item(d, patch)], _stream_handle(d), check)
     return t
 
 

@@ -14,6 +14,7 @@
 // and the formula's value for its T, which bounds every later index — and writes only elements of the window; what is wrong costs the verdict (ZN_DEV_CORRUPT).
 #include "zn_patch_host.hpp"
 
+#include <algorithm>
 #include <memory>
 
 // zn_patch_wave_incl, skipped where no lane of the wave brings anything
@@ -330,13 +331,17 @@ int patch_build(const std::vector<PatchSrc>& items, std::vector<uint64_t>& lens,
                            [](const ZnPatchBSeg& one, const ZnPatchBSeg* d, uint32_t n, uint32_t g, uint32_t* wd, uint32_t*, hipStream_t st) { zn_launch_patch_emit(one, d, n, g, wd, st); });
 }
 
-// what an apply call or plan works out before its first launch
-struct PatchApplySet {
-  std::vector<ZnPatchASeg> segs;
+// what an apply call or plan works out before its first launch (S: ZnPatchASeg, or ZnPatchLSeg for the strided call, which has no copies)
+template <typename S>
+struct PatchSet {
+  std::vector<S> segs;
   struct Copy { void* dst; const void* src; size_t n; };
   std::vector<Copy> copies;                      // items with d_base: the window's bytes of the base go to the destination first
   uint64_t total_wg = 0;
 };
+typedef PatchSet<ZnPatchASeg> PatchApplySet;
+void patch_launch_kernel(const ZnPatchASeg& one, const ZnPatchASeg* d, uint32_t n, uint32_t wg, uint32_t* st, hipStream_t s) { zn_launch_patch_apply(one, d, n, wg, st, s); }
+void patch_launch_kernel(const ZnPatchLSeg& one, const ZnPatchLSeg* d, uint32_t n, uint32_t wg, uint32_t* st, hipStream_t s) { zn_launch_patch_apply_strided(one, d, n, wg, st, s); }
 int patch_apply_segments(const zn_patch_apply_item* items, size_t count, PatchApplySet& A) {
   if (count && !items) return ZN_E_ARG;
   if (count > 0x7FFFFFFFull) return ZN_E_ARG;
@@ -359,7 +364,8 @@ int patch_apply_segments(const zn_patch_apply_item* items, size_t count, PatchAp
 }
 
 // the launches of an apply: d_table null = the table is staged through the pinned buffer (or, for one item, travels as the kernel's argument)
-int patch_apply_launch(const PatchApplySet& A, const ZnPatchASeg* d_table, hipStream_t stream, int check) {
+template <typename S>
+int patch_apply_launch(const PatchSet<S>& A, const S* d_table, hipStream_t stream, int check) {
   if (A.total_wg == 0 && A.copies.empty()) return ZN_OK;
   WsLease L;
   if (L.rc) return L.rc;
@@ -367,7 +373,7 @@ int patch_apply_launch(const PatchApplySet& A, const ZnPatchASeg* d_table, hipSt
   t_kernels.clear();
   int rc;
   const bool staged = A.segs.size() > 1 && !d_table && A.total_wg;
-  const size_t table_bytes = A.segs.size() * sizeof(ZnPatchASeg);
+  const size_t table_bytes = A.segs.size() * sizeof(S);
   if ((rc = w.reserve(WS_WORDS, ZN_WORDS_BYTES))) return rc;
   if ((rc = w.host_words())) return rc;
   if (staged && (rc = w.reserve(WS_SEGS, table_bytes))) return rc;
@@ -376,21 +382,65 @@ int patch_apply_launch(const PatchApplySet& A, const ZnPatchASeg* d_table, hipSt
   bool chain;
   uint32_t* d_status = zn_take_status_slot(w, L.dev, check, &chain);
   if (!chain) ZN_HIP(hipMemsetAsync(d_status, 0, 4 * sizeof(uint32_t), stream));      // (chained: the status word is the sequence's)
-  for (const PatchApplySet::Copy& c : A.copies)
+  for (const typename PatchSet<S>::Copy& c : A.copies)
     if (c.dst != c.src) ZN_HIP(hipMemcpyAsync(c.dst, c.src, c.n, hipMemcpyDeviceToDevice, stream));
   if (staged) {
     ZN_HIP(hipEventSynchronize(w.busy));         // the previous batched call may still be reading the pinned staging
     if ((rc = w.h_segs.reserve(table_bytes))) return rc;
     if ((rc = zn_patch_stage(w, A.segs.data(), table_bytes, 0, stream))) return rc;
-    d_table = (const ZnPatchASeg*)w.buf[WS_SEGS];
+    d_table = (const S*)w.buf[WS_SEGS];
   }
-  if (A.total_wg) zn_launch_patch_apply(A.segs[0], A.segs.size() > 1 ? d_table : nullptr, (uint32_t)A.segs.size(), (uint32_t)A.total_wg, d_status, stream);
+  if (A.total_wg) patch_launch_kernel(A.segs[0], A.segs.size() > 1 ? d_table : nullptr, (uint32_t)A.segs.size(), (uint32_t)A.total_wg, d_status, stream);
   if (launch_failed()) return ZN_E_HIP;
   if (check) {
     ZN_HIP(hipMemcpyAsync(w.h_status, d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     ZN_HIP(hipStreamSynchronize(stream));
     return status_to_rc(*w.h_status);
   }
+  return ZN_OK;
+}
+
+// One item of the strided call -> its segment, the layout CANONICAL: dimensions of size 1 dropped, neighbours merged where stride[i] == size[i + 1] stride[i + 1]
+// (a contiguous tensor becomes one dimension of stride 1, a single element none).  What remains must be INJECTIVE by the sufficient test: sorted by stride,
+// every stride exceeds the sum over the smaller ones of (size - 1) stride — each dimension steps past everything the smaller ones span —, and no stride is 0.
+// That refuses expand() and overlapping as_strided views, and some injective layouts too (interleaved ones).  The largest offset stays below 2^62 elements.
+int patch_strided_segment(const zn_patch_apply_strided_item& it, ZnPatchLSeg& sg, bool& contiguous) {
+  if (it.ndim < 0 || it.ndim > (int)ZN_PATCH_LAYOUT_DIMS || !zn_patch_elem_ok(it.n, it.elem)) return ZN_E_ARG;
+  if (!zn_patch_input_ok(it.d_patch, it.patch_len)) return ZN_E_ARG;
+  if (it.n && (!it.d_dst || !patch_aligned(it.d_dst, it.elem))) return ZN_E_ARG;
+  const uint64_t m = it.n / (size_t)it.elem;
+  uint64_t prod = 1;
+  unsigned __int128 reach = 0;                   // the last element's offset
+  for (int d = 0; d < it.ndim; d++) {
+    const uint64_t sz = it.size[d];
+    if (it.stride[d] < 0) return ZN_E_ARG;
+    if (prod && sz && prod > ~0ull / sz) return ZN_E_ARG;
+    prod *= sz;
+    if (sz) reach += (unsigned __int128)(sz - 1u) * (uint64_t)it.stride[d];
+  }
+  if (prod != m) return ZN_E_ARG;
+  sg = ZnPatchLSeg{(const uint8_t*)it.d_patch, it.patch_len, it.n, (uint8_t*)it.d_dst, {}, {}, 0u, (uint32_t)it.elem, 0u, 0u};
+  contiguous = true;
+  if (m == 0) return ZN_OK;                      // (no element, no workgroup: nothing is written)
+  if (reach >> 62) return ZN_E_ARG;
+  uint32_t k = 0;
+  for (int d = 0; d < it.ndim; d++) {
+    const uint64_t sz = it.size[d], st = (uint64_t)it.stride[d];      // (sz <= m < 2^32; sz st <= 2 reach)
+    if (sz == 1u) continue;
+    if (k && sg.stride[k - 1u] == sz * st) { sg.size[k - 1u] *= (uint32_t)sz; sg.stride[k - 1u] = st; }
+    else { sg.size[k] = (uint32_t)sz; sg.stride[k] = st; k++; }
+  }
+  sg.ndim = k;
+  uint32_t order[ZN_PATCH_LAYOUT_DIMS];
+  for (uint32_t i = 0; i < k; i++) order[i] = i;
+  std::sort(order, order + k, [&](uint32_t a, uint32_t b) { return sg.stride[a] < sg.stride[b]; });
+  uint64_t span = 0;
+  for (uint32_t i = 0; i < k; i++) {
+    const uint32_t d = order[i];
+    if (sg.stride[d] <= span) return ZN_E_ARG;
+    span += (uint64_t)(sg.size[d] - 1u) * sg.stride[d];
+  }
+  contiguous = k == 0 || (k == 1u && sg.stride[0] == 1u);
   return ZN_OK;
 }
 
@@ -447,7 +497,33 @@ int zn_patch_apply_batch_dev(const zn_patch_apply_item* items, size_t count, voi
   try {
     PatchApplySet A;
     const int rc = patch_apply_segments(items, count, A);
-    return rc ? rc : patch_apply_launch(A, nullptr, (hipStream_t)stream_, check);
+    return rc ? rc : patch_apply_launch<ZnPatchASeg>(A, nullptr, (hipStream_t)stream_, check);
+  } catch (...) { return ZN_E_ALLOC; }
+}
+
+int zn_patch_apply_strided_batch_dev(const zn_patch_apply_strided_item* items, size_t count, void* stream_, int check) {
+  try {
+    if (count && !items) return ZN_E_ARG;
+    if (count > 0x7FFFFFFFull) return ZN_E_ARG;
+    PatchSet<ZnPatchLSeg> A;
+    A.segs.resize(count);
+    bool all_contiguous = true;
+    for (size_t i = 0; i < count; i++) {
+      bool contiguous;
+      const int rc = patch_strided_segment(items[i], A.segs[i], contiguous);
+      if (rc) return rc;
+      all_contiguous = all_contiguous && contiguous;
+      A.segs[i].wg0 = (uint32_t)A.total_wg;
+      A.total_wg += zn_patch_blocks(items[i].n / (size_t)items[i].elem);
+      if (A.total_wg > 0x7FFFFFFFull) return ZN_E_ARG;
+    }
+    if (!all_contiguous) return patch_apply_launch<ZnPatchLSeg>(A, nullptr, (hipStream_t)stream_, check);
+    // every layout collapsed to the tensor itself: the contiguous launch, whole windows in place
+    std::vector<zn_patch_apply_item> plain(count);
+    for (size_t i = 0; i < count; i++) plain[i] = zn_patch_apply_item{items[i].d_patch, items[i].patch_len, items[i].n, items[i].elem, 0u, items[i].n, items[i].d_dst, nullptr};
+    PatchApplySet P;
+    const int rc = patch_apply_segments(plain.data(), count, P);
+    return rc ? rc : patch_apply_launch<ZnPatchASeg>(P, nullptr, (hipStream_t)stream_, check);
   } catch (...) { return ZN_E_ALLOC; }
 }
 

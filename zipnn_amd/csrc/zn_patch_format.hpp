@@ -1,6 +1,6 @@
 // zn_patch_format.hpp — the "znp1" patch format (include/zipnn_hip.h) in ONE place: its constants and layout, the items of the patch launches, and
-// the device-side tests every kernel that reads or writes a patch goes through.  Included by the three patch units (zn_patch.hip, zn_patch_merge.hip,
-// zn_patch_select.hip) and nobody else; the host side of their entry points is zn_patch_host.hpp.
+// the device-side tests every kernel that reads or writes a patch goes through.  Included by the four patch units (zn_patch.hip, zn_patch_merge.hip,
+// zn_patch_select.hip, zn_patch_strided.hip) and nobody else; the host side of their entry points is zn_patch_host.hpp.
 #pragma once
 
 #include "zn_common.hpp"
@@ -46,6 +46,29 @@ void zn_launch_patch_merge_emit(const ZnPatchMSeg& one, const ZnPatchMSeg* d_seg
 struct ZnPatchSSeg { const uint8_t* in; uint64_t in_len; uint8_t* out; uint32_t R, C, r0, r1, c0, c1; uint32_t wg0; uint32_t w0; uint32_t E; uint32_t pad_; };
 void zn_launch_patch_select_count(bool place, const ZnPatchSSeg& one, const ZnPatchSSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_words, uint32_t* d_status, hipStream_t stream);
 void zn_launch_patch_select_emit(bool place, const ZnPatchSSeg& one, const ZnPatchSSeg* d_segs, uint32_t nseg, uint32_t total_wg, const uint32_t* d_words, uint32_t* d_status, hipStream_t stream);
+// ---- a patch applied through a strided layout : zn_patch_strided.hip ----
+#define ZN_PATCH_LAYOUT_DIMS 8u              // ZN_PATCH_MAX_DIMS of include/zipnn_hip.h
+// Where element e of the logical row-major order lies, in elements from logical element 0: e unravelled over size[0 .. ndim) (the last dimension fastest) and
+// dotted with the strides.  e < the product of the sizes, which is below 2^32, so every quotient fits 32 bits and the divisions are 32-bit ones (there is no
+// hardware integer divide: a 64-bit one costs several times a 32-bit one); only the products with the strides are 64-bit — a view of a large buffer spans more
+// than 2^32 elements.  Dimension 0 needs no division: what is left of e is its coordinate.  The loop is unrolled over constant indices, so that sizes and
+// strides — wave-uniform in the kernel — stay in registers.  Touches no memory: the stand-alone host test calls it with layouts that have none behind them.
+__host__ __device__ static inline uint64_t zn_patch_layout_offset(uint32_t ndim, const uint32_t (&size)[ZN_PATCH_LAYOUT_DIMS], const uint64_t (&stride)[ZN_PATCH_LAYOUT_DIMS], uint32_t e) {
+  uint64_t at = 0;
+#pragma unroll
+  for (uint32_t d = ZN_PATCH_LAYOUT_DIMS - 1u; d >= 1u; d--)
+    if (d < ndim) {
+      const uint32_t q = e / size[d];
+      at += (uint64_t)(e - q * size[d]) * stride[d];
+      e = q;
+    }
+  if (ndim) at += (uint64_t)e * stride[0];
+  return at;
+}
+// One item of a strided apply launch: the patch, the tensor it describes (n bytes, E per element), where LOGICAL element 0 lies (dst) and the layout as the host
+// has collapsed it (ndim <= 8 dimensions, no size 1, no stride 0, injective; the sizes' product is n / E); its first workgroup — one per block of the tensor.
+struct ZnPatchLSeg { const uint8_t* patch; uint64_t patch_len; uint64_t n; uint8_t* dst; uint64_t stride[ZN_PATCH_LAYOUT_DIMS]; uint32_t size[ZN_PATCH_LAYOUT_DIMS]; uint32_t wg0; uint32_t E; uint32_t ndim; uint32_t pad_; };
+void zn_launch_patch_apply_strided(const ZnPatchLSeg& one, const ZnPatchLSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_status, hipStream_t stream);
 
 #if defined(__HIPCC__) || defined(ZN_SIMT_EMULATOR)
 template <uint32_t E> struct ZnPatchElem;

@@ -98,7 +98,8 @@ _stream_of, _device_of = codec._stream_of, codec._device_of
 # The kinds of launch set (_launch_sets) and the ZnLib methods that serve each: (the batched call, plan create, plan run, plan destroy)
 _KINDS = {"window": ("decompress_window_batch_dev", "plan_create", "plan_run", "plan_destroy"),
           "hinted": ("decompress_hinted_batch_dev", "plan_create_hinted", "plan_run", "plan_destroy"),
-          "patch": ("patch_apply_batch_dev", "patch_plan_create", "patch_plan_run", "patch_plan_destroy")}
+          "patch": ("patch_apply_batch_dev", "patch_plan_create", "patch_plan_run", "patch_plan_destroy"),
+          "strided": ("patch_apply_strided_batch_dev", None, None, None)}      # sparse entries on non-contiguous live tensors: a batched call only
 
 
 def _launch(lib, steps, stream, check):
@@ -267,6 +268,8 @@ class ResidentCheckpoint:
         ft.info(n)["delta"], ft.info(n)["patch_entries"]                                          # "sparse", the number of elements that differ
         flat = s3.rebased(base); sw = ft_b.rebased(ft_a)      # the same tensors over another store: a chain flattened, a sibling re-parented — by patch merges
         mine = ft.sharded(base_shards, {name: (dim, lo, hi)})     # one tensor-parallel rank's narrow() of every tensor, over its shard of the base — patches are selected, not decoded
+
+        ft.apply_({"o_proj.weight": live.t(), "up_proj.weight": fused[:, a:b]})     # live tensors at any strides that pass the injectivity test; ft.patch(name) for other shapes
 
     CONTENT DIGESTS ("zn64-1"; an error-detecting code, not a cryptographic hash) let a store answer whether what it decodes is still what it was built from:
 
@@ -913,9 +916,35 @@ class ResidentCheckpoint:
     def _run_sets(self, sets, check):
         """The calls of _launch_sets, in order, on the current stream.  check=False: the sets behind the first add their verdict to the first's
         (zn_decode_status_chain), so that status() speaks for all of them."""
+        self._run_steps(self._set_steps(sets), check)
+
+    @staticmethod
+    def _set_steps(sets):
+        """launch sets -> the steps of _launch: [(the batched call of the set's kind, its items, None)]"""
         lib = _capi.lib()
+        return [(getattr(lib, _KINDS[kind][0]), items, None) for kind, items in sets]
+
+    def _run_steps(self, steps, check):
         with _device_of(self.device):
-            _launch(lib, [(getattr(lib, _KINDS[kind][0]), items, None) for kind, items in sets], _stream_of(self.device), check)
+            _launch(_capi.lib(), steps, _stream_of(self.device), check)
+
+    def _scratch_steps(self, todo):
+        """todo: [(store, entry of it, live tensor)] — non-contiguous live tensors that receive a decoded tensor -> the steps of _launch that
+        decode each entry through its store's normal path into ONE scratch buffer and follow with a stride-aware copy_ into the live tensor, grouped as verify()
+        groups: never more scratch than the largest such tensor, and the stream orders the buffer's reuse."""
+        if not todo:
+            return []
+        scratch = torch.empty(max(_round_up(e.nbytes) for _, e, _ in todo), dtype=torch.uint8, device=self.device)
+        steps = []
+        for grp in _groups(todo, lambda it: _round_up(it[1].nbytes), scratch.numel()):
+            flats = [scratch[o:o + e.nbytes] for (_, e, _), o in zip(grp, _packed(e.nbytes for _, e, _ in grp)[0])]
+            via = {}
+            for (store, e, _), flat in zip(grp, flats):
+                via.setdefault(id(store), (store, []))[1].append((e, 0, e.chunks, flat))
+            for store, w in via.values():
+                steps += self._set_steps(store._launch_sets(w))
+            steps.append((lambda pairs, stream, check: [t.copy_(e.view(flat)) for t, e, flat in pairs], [(t, e, flat) for (_, e, t), flat in zip(grp, flats)], None))
+        return steps
 
     def _decode(self, work, check):
         """work: [(entry, chunk_lo, chunk_hi, flat uint8 destination)] -> batched decodes on the current stream, hinted where an entry has an index; one
@@ -1165,12 +1194,37 @@ class ResidentCheckpoint:
         return res
 
     def _live_digests(self, pairs):
-        """[(key, tensor)] -> {key: digest of the live tensor's bytes}: one batched launch, one read-back."""
-        return dict(zip([k for k, _ in pairs], codec.digests_of(_capi.lib(), [t for _, t in pairs], _stream_of(self.device))))
+        """[(key, tensor)] -> {key: digest of the live tensor's LOGICAL bytes}: contiguous tensors digested where they lie by one batched launch; non-contiguous
+        ones through a contiguous copy — what zipnn_amd.digest does —, the copies grouped in one scratch buffer sized for the largest of them, one
+        digest launch per group behind its copies on the current stream; one read-back."""
+        lib = _capi.lib()
+        here = [(k, t) for k, t in pairs if t.is_contiguous()]
+        there = [(k, t) for k, t in pairs if not t.is_contiguous()]
+        if not there:
+            return dict(zip([k for k, _ in here], codec.digests_of(lib, [t for _, t in here], _stream_of(self.device))))
+
+        def size(kt):
+            return _round_up(kt[1].numel() * kt[1].element_size())
+        out = torch.empty(len(pairs), dtype=torch.int64, device=self.device)
+        with _device_of(self.device):
+            stream = _stream_of(self.device)
+            if here:
+                codec.digest_device_batch(lib, [codec.flat_bytes(t) for _, t in here], stream, out=out[:len(here)])
+            scratch = torch.empty(max(size(kt) for kt in there), dtype=torch.uint8, device=self.device)
+            k = len(here)
+            for grp in _groups(there, size, scratch.numel()):
+                flats = [scratch[o:o + t.numel() * t.element_size()] for (_, t), o in zip(grp, _packed(t.numel() * t.element_size() for _, t in grp)[0])]
+                for (_, t), flat in zip(grp, flats):
+                    flat.view(t.dtype).reshape(t.shape).copy_(t)
+                codec.digest_device_batch(lib, flats, stream, out=out[k:k + len(grp)])
+                k += len(grp)
+            vals = codec.digests_to_ints(out)
+        return dict(zip([k for k, _ in here + there], vals))
 
     def holds(self, target):
-        """Do live tensors hold this store's values?  target: a module (named parameters and buffers) or a mapping of names to contiguous tensors on the
-        store's device.  -> {name: bool} for the names the store has: the live tensors digested where they lie (one launch), compared with the recorded digests."""
+        """Do live tensors hold this store's values?  target: a module (named parameters and buffers) or a mapping of names to tensors on the store's device, at
+        any strides apply_ accepts.  -> {name: bool} for the names the store has: the live tensors digested where they lie (one launch; non-contiguous ones
+        through grouped contiguous copies, _live_digests), compared with the recorded digests."""
         self._need_digests()
         tg = self._targets(target)
         live = self._live_digests([(e.name, t) for e, t in tg])
@@ -1203,34 +1257,43 @@ class ResidentCheckpoint:
 
     # ---- a variant applied to live weights ------------------------------------------------------------------------------------
     def _targets(self, target):
-        """target: a module (named parameters and buffers) or a mapping -> [(entry, tensor)] for the names the store has."""
+        """target: a module (named parameters and buffers) or a mapping -> [(entry, tensor)] for the names the store has.  A tensor has the entry's dtype and
+        shape and lies on the store's device: contiguous, or a strided view of live memory — a transposed weight, a column slice of a fused buffer, a permuted
+        layout — whose strides pass the injectivity test of zn_patch_apply_strided_batch_dev (expand()ed and overlapping views are refused)."""
         out = []
         for name, t in _named_tensors(target).items():
             e = self._entries.get(name)
             if e is None:
                 continue
             t = t.detach()
-            if t.dtype != e.dtype or tuple(t.shape) != e.shape or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"{name}: a contiguous {e.dtype} tensor of shape {list(e.shape)} on {self.device}")
+            if t.dtype != e.dtype or tuple(t.shape) != e.shape or t.device != self.device:
+                raise ValueError(f"{name}: a {e.dtype} tensor of shape {list(e.shape)} on {self.device}")
+            why = None if t.is_contiguous() else codec.patch_layout_refusal(t)
+            if why:
+                raise ValueError(f"{name}: the view cannot be written in place: {why}")
             out.append((e, t))
         return out
 
     def _in_place_sets(self, target):
         """What apply_ and revert_ share: the target's tensors that differ from the base's ("same" and empty entries do not) -> (the launch sets that XOR delta
         bodies and patches into them IN PLACE — the same call both ways —, [(entry, tensor)] of the others: entries with a body or a tensor of their own, the
-        names of all of them)."""
-        inplace, patch, rest, names = [], [], [], []
+        names of all of them).  A sparse entry on a NON-CONTIGUOUS tensor is patched through its layout (a "strided" set) and is in place all the
+        same; a delta entry on one has no in-place decode and joins the others: it is overwritten by a decode, not XORed."""
+        inplace, patch, strided, rest, names = [], [], [], [], []
         for e, t in self._targets(target):
             if e.delta == "same" or not e.nbytes:
                 continue
-            if e.delta is True:
+            if e.delta == "sparse":
+                if t.is_contiguous():
+                    patch.append(e.patch_item(0, e.chunks, t.data_ptr()))
+                else:
+                    strided.append(codec.patch_strided_item(t, e.patch))
+            elif e.delta is True and t.is_contiguous():
                 inplace.append((e, 0, e.chunks, t.data_ptr(), t.data_ptr()))
-            elif e.delta == "sparse":
-                patch.append(e.patch_item(0, e.chunks, t.data_ptr()))
             else:
                 rest.append((e, t))
             names.append(e.name)
-        return self._delta_sets(inplace) + ([("patch", patch)] if patch else []), rest, names
+        return self._delta_sets(inplace) + ([("patch", patch)] if patch else []) + ([("strided", strided)] if strided else []), rest, names
 
     def apply_(self, target, check=True, guard=False):
         """Turn live BASE weights into the fine-tune's, in place: `target` is a module or a mapping of names to contiguous tensors on the store's device that
@@ -1239,17 +1302,24 @@ class ResidentCheckpoint:
         plain entries are overwritten, "same" entries are left alone; one batched launch set on the current stream.
         Nothing is tracked: applying twice (or to tensors that do not hold the base) XORs the delta in twice and is the caller's mistake — unless guard=True
         (a store with digests): the live tensors are digested first and must hold the BASE's values, else DigestMismatch is raised before anything is touched.  If `target` is
-        the very tensors this store holds as its plain base, the store decodes wrong values until revert_.  -> the names changed."""
+        the very tensors this store holds as its plain base, the store decodes wrong values until revert_.  -> the names changed.
+        NON-CONTIGUOUS targets — {"o_proj.weight": live.t(), "up_proj.weight": fused[:, a:b]}, any strided view of the entry's dtype and shape
+        whose strides pass zn_patch_apply_strided_batch_dev's injectivity test: a sparse entry is patched through the view's layout, in place, by one more batched
+        launch; a plain entry, and a DELTA entry, is decoded through the store's normal path into a scratch buffer (grouped: never more than the largest such
+        tensor) and copied in by a stride-aware copy_ — for a delta entry that OVERWRITES instead of XORing, which is the same whenever the target held what
+        apply_ requires, the base's values.  revert_ does the same with the base's tensors."""
         if guard:
             self._guard(target, True)
         sets, rest, done = self._in_place_sets(target)
-        work = []
+        work, scratch = [], []
         for e, t in rest:
-            if e.compressed:
+            if e.compressed and not t.is_contiguous():
+                scratch.append((self, e, t))
+            elif e.compressed:
                 work.append((e, 0, e.chunks, codec.flat_bytes(t)))
             else:
                 t.copy_(e.raw)
-        self._run_sets(self._launch_sets(work) + sets, check)
+        self._run_steps(self._scratch_steps(scratch) + self._set_steps(self._launch_sets(work) + sets), check)
         return done
 
     def revert_(self, target, check=True, guard=False):
@@ -1260,20 +1330,33 @@ class ResidentCheckpoint:
         if guard:
             self._guard(target, False)
         sets, rest, _ = self._in_place_sets(target)
-        stay, via = [], {}
+        stay, via, scratch = [], {}, []
         for e, t in rest:
-            ref = e.restore
+            ref = e.base if e.delta is True else e.restore      # (a delta entry is here with a non-contiguous target: what it decodes over is what it goes back to)
             if ref is None or (ref.tensor is not None and ref.tensor.data_ptr() == t.data_ptr()):      # (nothing to restore from, or the base's tensor IS the target: its values are gone)
                 stay.append(e.name)
             elif ref.tensor is not None:
                 t.copy_(ref.tensor)
+            elif not t.is_contiguous():
+                scratch.append((ref.store, ref.entry, t))
             else:
                 via.setdefault(id(ref.store), (ref.store, []))[1].append((ref.entry, 0, ref.entry.chunks, codec.flat_bytes(t)))
         base_sets = []
         for bstore, w in via.values():
             base_sets += bstore._launch_sets(w)
-        self._run_sets(base_sets + sets, check)
+        self._run_steps(self._scratch_steps(scratch) + self._set_steps(base_sets + sets), check)
         return stay
+
+    def patch(self, name):
+        """The "znp1" patch of a sparse entry: a uint8 view of the store's own memory — read it, do not write to it —, or None for a "same" entry (nothing
+        differs from the base).  What zipnn_amd.patch_apply_ takes: through it a caller reaches live layouts with ANOTHER shape than the entry's (a tile-shuffled
+        weight through the N-D view that undoes the shuffle).  KeyError: no such tensor; ValueError: the entry is neither sparse nor "same"."""
+        e = self._entries[name]
+        if e.delta == "same":
+            return None
+        if e.delta != "sparse":
+            raise ValueError(f"{name}: not a sparse entry (delta: {e.delta!r})")
+        return e.patch.detach()
 
     # ---- model integration ----------------------------------------------------------------------------------------------------
     def hook(self, model, modules=None):
