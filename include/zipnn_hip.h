@@ -352,7 +352,19 @@ int zn_digest_host(const void* src, size_t n, unsigned long long* out);
  *   refuses expand() and overlapping as_strided views, and also injective views whose dimensions interleave.  ZN_E_ARG before any launch: ndim outside
  *   0 .. ZN_PATCH_MAX_DIMS, a product of the sizes that is not n / elem, a negative stride, a layout that fails the test or whose last element lies 2^62
  *   elements or more from the first, an (n, elem) that is not eligible, d_dst null with n > 0 or not elem-aligned, d_patch null or not 16-byte aligned,
- *   patch_len < 32.  A patch with T == 0 and a tensor with n == 0 are valid and write nothing. */
+ *   patch_len < 32.  A patch with T == 0 and a tensor with n == 0 are valid and write nothing.
+ * zn_patch_size_strided_batch_dev / zn_patch_build_strided_batch_dev: zn_patch_size_batch_dev / zn_patch_build_batch_dev for a source and a base that are STRIDED
+ *   VIEWS: what a trainer left in an engine's own layout, against the base in its own — two stride lists over one logical shape, d_src / d_base
+ *   where LOGICAL element 0 of each lies.  The same semantics: count, scan, one read-back, emit; ZN_E_CAP with the needed lengths and nothing written;
+ *   patch_len == 0 for identical bytes; synchronous.  The result is BYTE FOR BYTE the patch zn_patch_build_batch_dev gives for contiguous copies of the two
+ *   views; no copy is made (zn_k_patch_count_strided, zn_k_patch_scan, zn_k_patch_emit_strided: one workgroup per block of every item, both sides read through
+ *   their layouts).  The host makes the two layouts canonical JOINTLY — dimensions of size 1 dropped, neighbours merged only where both stride lists merge —;
+ *   a batch whose items all collapse to contiguous tensors on both sides takes zn_patch_build_batch_dev's launches.  Views are only READ: there is no
+ *   injectivity test, expand() (a stride of 0) and overlapping views are accepted.  ZN_E_ARG before any launch: ndim outside 0 .. ZN_PATCH_MAX_DIMS, a product
+ *   of the sizes that is not n / elem, a negative stride, a last element 2^62 elements or more from the first, an (n, elem) that is not eligible, d_src or
+ *   d_base null with n > 0 or not elem-aligned, a d_patch (with patch_cap > 0) that is not 16-byte aligned, or whose [d_patch, d_patch + patch_cap) overlaps
+ *   the address span — first to last element — of either view.  The views must not change during the call; if they do the patch is wrong, never the memory
+ *   around it. */
 #define ZN_PATCH_BAD_HEADER 1u
 #define ZN_PATCH_BAD_FIRST 2u
 #define ZN_PATCH_BAD_OFFSET 4u
@@ -386,6 +398,16 @@ typedef struct zn_patch_apply_strided_item {
   int ndim; unsigned long long size[ZN_PATCH_MAX_DIMS]; long long stride[ZN_PATCH_MAX_DIMS];   /* strides in elements */
 } zn_patch_apply_strided_item;
 int zn_patch_apply_strided_batch_dev(const zn_patch_apply_strided_item* items, size_t count, void* stream, int check);
+typedef struct zn_patch_build_strided_item {
+  const void* d_src; const void* d_base;    /* where LOGICAL element 0 of each lies; elem-aligned */
+  size_t n; int elem; int ndim;             /* the tensor: n bytes, elements of elem; ONE logical shape … */
+  unsigned long long size[ZN_PATCH_MAX_DIMS];
+  long long src_stride[ZN_PATCH_MAX_DIMS], base_stride[ZN_PATCH_MAX_DIMS];   /* … and a layout of its own for each side, strides in elements */
+  void* d_patch; size_t patch_cap;          /* 16-byte aligned; unused by the size call */
+  size_t patch_len;                         /* out (the build call) */
+} zn_patch_build_strided_item;
+int zn_patch_size_strided_batch_dev(const zn_patch_build_strided_item* items, size_t count, size_t* sizes_out, void* stream);
+int zn_patch_build_strided_batch_dev(zn_patch_build_strided_item* items, size_t count, void* stream);
 typedef struct zn_patch_check_item { const void* d_patch; size_t patch_len; size_t n; int elem; } zn_patch_check_item;
 int zn_patch_check_batch_dev(const zn_patch_check_item* items, size_t count,
                              unsigned int* verdicts_out,        /* host, one per item: 0 = well-formed */

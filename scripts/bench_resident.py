@@ -1238,6 +1238,152 @@ def main_strided(args):
     return 0
 
 
+LOGICAL_LIB = os.path.join(ROOT, "zipnn_amd", "libzipnn_hip_ab_logical.so")      # build_extension(defines=("ZN_PATCH_BUILD_LOGICAL_ORDER",), out=LOGICAL_LIB)
+
+
+def leg_c(args):
+    """--capture: patches of one Llama-3-8B block of a 2 % fine-tune BUILT from live tensors in four layouts against a plain-tensor base:
+    the strided build call against contiguous() on every view + the contiguous build call; the same call through the library built with
+    -DZN_PATCH_BUILD_LOGICAL_ORDER (load order (i), the baseline) where that library exists; from_live against from_state_dict on contiguous copies, with both builds' peak
+    allocated memory above the resting level."""
+    import torch
+    from zipnn_amd import ResidentCheckpoint, _capi, codec
+    lib = _capi.lib()
+    logical = _capi.ZnLib(LOGICAL_LIB) if os.path.exists(LOGICAL_LIB) else None
+    sd, per = _blocks(1)
+    names = per[0]
+    ft = _fine_tune(sd, "sparse", 21)
+
+    def live_of(layout):
+        out = {}
+        for k in names:
+            w = ft[k]
+            if layout == "contiguous" or w.dim() != 2:
+                out[k] = w.clone()
+            elif layout == "transposed":
+                out[k] = w.t().contiguous().t()
+            elif layout == "narrow":
+                fused = torch.zeros(w.shape[0], 2 * w.shape[1], dtype=w.dtype, device=w.device)
+                out[k] = fused[:, w.shape[1] // 2: w.shape[1] // 2 + w.shape[1]]
+                out[k].copy_(w)
+            else:                                             # "tile": tile-shuffled storage seen through the view whose row-major order is the tensor's, reshaped back to 2-D where torch can
+                R, C = w.shape
+                out[k] = w.view(R // 16, 16, C // 32, 32).permute(0, 2, 1, 3).contiguous().permute(0, 2, 1, 3)
+        return out
+
+    def base_of(live, k):
+        return sd[k].view(live[k].shape)
+
+    def peak(fn):
+        torch.cuda.synchronize(); torch.cuda.reset_peak_memory_stats()
+        rest = torch.cuda.memory_allocated()
+        out = fn()
+        torch.cuda.synchronize()
+        return torch.cuda.max_memory_allocated() - rest, out
+
+    res = {"block_bytes": sum(sd[k].numel() * 2 for k in names), "tensors": len(names), "logical": logical is not None, "layouts": []}
+    want = None
+    for layout in ("contiguous", "transposed", "narrow", "tile"):
+        live = live_of(layout)
+        pairs = [(live[k], base_of(live, k)) for k in names]
+        fns = {"strided": lambda: codec.patch_build_strided_device_batch(lib, pairs),
+               "workaround": lambda: codec.patch_build_device_batch(lib, [(codec.flat_bytes(s.contiguous()), codec.flat_bytes(b), 2) for s, b in pairs])}
+        if logical is not None:
+            fns["logical"] = lambda: codec.patch_build_strided_device_batch(logical, pairs)
+        got, kernels = {}, {}
+        for leg, fn in fns.items():                           # each leg's kernels, read directly behind its call
+            got[leg] = [None if p is None else p.clone() for p in fn()]
+            kernels[leg] = (logical if leg == "logical" else lib).last_kernels()
+        want = want or got["workaround"]
+        for leg, ps in got.items():                           # every leg, every layout: the same patches, byte for byte
+            assert all((a is None and b is None) or torch.equal(a, b) for a, b in zip(ps, want)), (layout, leg)
+        del got
+        order = list(fns) + list(fns) + list(reversed(fns)) + list(reversed(fns))
+        runs = {leg: [] for leg in fns}
+        for leg in order:
+            runs[leg].append(_events_ms(fns[leg], args.reps)["median_ms"])
+        targets = {k: live[k] for k in names}
+        base = {k: base_of(live, k) for k in names}
+        builds = {"from_live": lambda: ResidentCheckpoint.from_live(targets, base),
+                  "from_state_dict": lambda: ResidentCheckpoint.from_state_dict({n: v.contiguous() for n, v in targets.items()}, "cuda:0", base=base, sparse=True)}
+        bruns, peaks = {leg: [] for leg in builds}, {}
+        for leg in ("from_live", "from_state_dict", "from_state_dict", "from_live"):
+            bruns[leg].append(_events_ms(builds[leg], 2, warm=1)["median_ms"])
+        for leg, fn in builds.items():
+            peaks[leg], store = peak(fn)
+            kernels[leg] = _capi_kernels()                    # (the last patch call of the build)
+            assert all(_same(store.get_tensor(k), ft[k]) for k in names[:3]), (layout, leg)
+            kinds = sorted({str(store.info(k)["delta"]) for k in names})
+            del store
+        res["layouts"].append({"layout": layout, "runs_ms": runs, "median_ms": {k: statistics.median(v) for k, v in runs.items()}, "kernels": kernels,
+                               "build_runs_ms": bruns, "build_median_ms": {k: statistics.median(v) for k, v in bruns.items()}, "peak_bytes": peaks, "kinds": kinds})
+        del live, pairs, fns, targets, base, builds
+        torch.cuda.empty_cache()
+    res["aa_spread"] = max((max(v) - min(v)) / min(v) for r in res["layouts"] for v in r["runs_ms"].values())
+    res["aa_spread_builds"] = max((max(v) - min(v)) / min(v) for r in res["layouts"] for v in r["build_runs_ms"].values())
+    return res
+
+
+def main_capture(args):
+    p = subprocess.run(["timeout", "-k", "10", "840", sys.executable, os.path.abspath(__file__), "--leg", "c", "--reps", str(args.reps)], capture_output=True, text=True)
+    line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+    if p.returncode != 0 or not line:
+        print(f"leg c failed (exit {p.returncode})\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}")
+        return 1
+    res = json.loads(line[0][7:])
+    out = args.out if args.out != os.path.join(ROOT, "profiles", "resident_decode") else os.path.join(ROOT, "profiles", "patch_build_strided")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    sp, spb = res["aa_spread"], res["aa_spread_builds"]
+    lines = [f"command: python scripts/bench_resident.py --capture --reps {args.reps}",
+             f"strided build probe (zn_patch_build_strided_batch_dev and ResidentCheckpoint.from_live, DESIGN §3.16): one Llama-3-8B block ({res['tensors']} tensors, {res['block_bytes']} B, bf16) of a 2 % fine-tune,",
+             f"live in four layouts, against plain base tensors; device events, median ms of {args.reps} calls per run; the runs of a layout interleaved in both orders; every leg's patches are byte-equal.",
+             "strided: one zn_patch_build_strided_batch_dev call, load order (ii) (along memory: the library's default).  workaround: contiguous() on every view + one zn_patch_build_batch_dev call.",
+             "logical: the strided call of the library built with -DZN_PATCH_BUILD_LOGICAL_ORDER, load order (i)." if res["logical"] else "logical: NOT MEASURED (no library built with -DZN_PATCH_BUILD_LOGICAL_ORDER beside this one)",
+             f"A/A spread (the largest (max - min) / min among the repeated runs of one leg on one layout): build calls {100 * sp:.1f} %, store builds {100 * spb:.1f} %"]
+    for r in res["layouts"]:
+        q, m = r["runs_ms"], r["median_ms"]
+        lines.append(f"  {r['layout']:<11} " + "   ".join(f"{leg} " + " / ".join(f"{x:.3f}" for x in q[leg]) for leg in q))
+        gain = 1.0 - m["strided"] / m["workaround"]
+        verdict = "beats the workaround by more than the spread" if gain > sp else "LOSES to the workaround" if gain < -sp else "inside the spread of the workaround"
+        lines.append(f"              medians: strided {m['strided']:.3f}, workaround {m['workaround']:.3f}: the strided call takes {m['strided'] / m['workaround']:.2f} of the workaround's time — {verdict}")
+        if "logical" in m:
+            g2 = 1.0 - m["strided"] / m["logical"]
+            lines.append(f"              load order (ii) {m['strided']:.3f} against (i) {m['logical']:.3f}: {'(ii) wins by more than the spread' if g2 > sp else '(ii) LOSES by more than the spread' if g2 < -sp else 'inside the spread'}"
+                         f"   [(i): {r['kernels']['logical']}]")
+        b, pk = r["build_median_ms"], r["peak_bytes"]
+        g3 = 1.0 - b["from_live"] / b["from_state_dict"]
+        lines.append(f"              from_live " + " / ".join(f"{x:.1f}" for x in r["build_runs_ms"]["from_live"]) + "   from_state_dict on contiguous copies " + " / ".join(f"{x:.1f}" for x in r["build_runs_ms"]["from_state_dict"]) +
+                     f" ms: {b['from_live'] / b['from_state_dict']:.3f} of its time — {'beats it by more than the spread' if g3 > spb else 'LOSES to it' if g3 < -spb else 'inside the spread'}; entries {r['kinds']}")
+        lines.append(f"              peak allocated above the resting level: from_live {pk['from_live']} B, from_state_dict {pk['from_state_dict']} B")
+        lines.append(f"              kernels: strided call [{r['kernels']['strided']}]  workaround [{r['kernels']['workaround']}]  from_live's last patch call [{r['kernels']['from_live']}]")
+    lines += _load_order_decision(res)
+    open(out + ".txt", "w").write("\n".join(lines) + "\n")
+    json.dump(res, open(out + ".json", "w"), indent=1)
+    print("\n".join(lines))
+    return 0
+
+
+def _load_order_decision(res):
+    """The load-order decision of DESIGN §3.16 from this run's own numbers.  Rule: (ii), the block walked along memory, is the default only if it beats (i), the
+    logical order, on the transposed layout by more than the run's A/A spread and loses on no other layout by more than that spread."""
+    if not res["logical"]:
+        return ["", "load-order decision: NOT MEASURED in this run (no logical-order library)"]
+    sp = res["aa_spread"]
+    gains = {r["layout"]: 1.0 - r["median_ms"]["strided"] / r["median_ms"]["logical"] for r in res["layouts"]}
+    wins = gains["transposed"] > sp
+    loses = [k for k, g in gains.items() if k != "transposed" and g < -sp]
+    t = next(r for r in res["layouts"] if r["layout"] == "transposed")["median_ms"]
+    out = ["", f"load-order decision (DESIGN §3.16), from this run; A/A spread of the build calls {100 * sp:.1f} %:",
+           f"  transposed: (ii) {t['strided']:.3f} ms against (i) {t['logical']:.3f} ms ({t['logical'] / t['strided']:.1f} x): " + ("beyond the spread" if wins else "NOT beyond the spread"),
+           "  the other layouts, (ii) against (i): " + ", ".join(f"{k} {100 * -g:+.1f} %" for k, g in gains.items() if k != "transposed") +
+           (": none loses by more than the spread" if not loses else f": LOSES on {', '.join(loses)}"),
+           "  -> " + ("(ii) is the default; (i) stays behind -DZN_PATCH_BUILD_LOGICAL_ORDER as the baseline" if wins and not loses else "the rule asks for (i)")]
+    against = {r["layout"]: 1.0 - r["median_ms"]["strided"] / r["median_ms"]["workaround"] for r in res["layouts"]}
+    out.append("  against the workaround (a gain or loss counts only beyond the spread): " +
+               ", ".join(f"{k} {'gains' if g > sp else 'LOSES' if g < -sp else 'inside the spread'} ({100 * -g:+.1f} %)" for k, g in against.items()))
+    return out
+
+
 def main_index(args):
     results = {}
     for leg, limit in INDEX_LEG_SECONDS.items():
@@ -1284,6 +1430,7 @@ def main():
     ap.add_argument("--rebase", action="store_true", help="the patch merge / rebased leg (r) instead of a-e")
     ap.add_argument("--shard", action="store_true", help="the patch select / sharded leg (h) instead of a-e")
     ap.add_argument("--strided", action="store_true", help="the strided apply leg (t) instead of a-e")
+    ap.add_argument("--capture", action="store_true", help="the strided build / from_live leg (c) instead of a-e")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resident_decode"))
     args = ap.parse_args()
     if args.leg:                                          # a child: one leg, its result as one JSON line
@@ -1309,6 +1456,8 @@ def main():
         return main_shard(args)
     if args.strided:
         return main_strided(args)
+    if args.capture:
+        return main_capture(args)
     results = {}
     for leg, limit in LEG_SECONDS.items():
         p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--layers", str(args.layers), "--reps", str(args.reps)],

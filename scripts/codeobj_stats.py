@@ -40,7 +40,8 @@ HOT = [("zn_k_decode_fusedILi1ELb0ELb0E", "decode_fused<1> plain"), ("zn_k_decod
        ("zn_k_patch_merge_count", "patch_merge_count (§3.12)"), ("zn_k_patch_merge_emit", "patch_merge_emit"),
        ("zn_k_patch_select_count", "patch_select_count (§3.13)"), ("zn_k_patch_select_emit", "patch_select_emit"),
        ("zn_k_patch_place_count", "patch_place_count"), ("zn_k_patch_place_emit", "patch_place_emit"),
-       ("zn_k_patch_apply_strided", "patch_apply_strided (§3.15)")]
+       ("zn_k_patch_apply_strided", "patch_apply_strided (§3.15)"),
+       ("zn_k_patch_count_strided", "patch_count_strided (§3.16)"), ("zn_k_patch_emit_strided", "patch_emit_strided")]
 
 
 def kernels_of(obj):

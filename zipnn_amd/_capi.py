@@ -112,6 +112,16 @@ class ZnPatchApplyStridedItem(ctypes.Structure):
 assert ctypes.sizeof(ZnPatchApplyStridedItem) == 176
 
 
+class ZnPatchBuildStridedItem(ctypes.Structure):
+    """struct zn_patch_build_strided_item of include/zipnn_hip.h"""
+    _fields_ = [("d_src", ctypes.c_void_p), ("d_base", ctypes.c_void_p), ("n", ctypes.c_size_t), ("elem", ctypes.c_int), ("ndim", ctypes.c_int),
+                ("size", ctypes.c_ulonglong * PATCH_MAX_DIMS), ("src_stride", ctypes.c_longlong * PATCH_MAX_DIMS), ("base_stride", ctypes.c_longlong * PATCH_MAX_DIMS),
+                ("d_patch", ctypes.c_void_p), ("patch_cap", ctypes.c_size_t), ("patch_len", ctypes.c_size_t)]
+
+
+assert ctypes.sizeof(ZnPatchBuildStridedItem) == 248
+
+
 class ZnPatchCheckItem(ctypes.Structure):
     """struct zn_patch_check_item of include/zipnn_hip.h"""
     _fields_ = [("d_patch", ctypes.c_void_p), ("patch_len", ctypes.c_size_t), ("n", ctypes.c_size_t), ("elem", ctypes.c_int)]
@@ -270,6 +280,11 @@ class ZnLib:
         if hasattr(L, "zn_patch_apply_strided_batch_dev"):      # (likewise: a library from before the strided apply)
             L.zn_patch_apply_strided_batch_dev.restype = ci
             L.zn_patch_apply_strided_batch_dev.argtypes = [ctypes.POINTER(ZnPatchApplyStridedItem), sz, vp, ci]
+        if hasattr(L, "zn_patch_build_strided_batch_dev"):      # (likewise: a library from before the strided build)
+            L.zn_patch_size_strided_batch_dev.restype = ci
+            L.zn_patch_size_strided_batch_dev.argtypes = [ctypes.POINTER(ZnPatchBuildStridedItem), sz, ctypes.POINTER(sz), vp]
+            L.zn_patch_build_strided_batch_dev.restype = ci
+            L.zn_patch_build_strided_batch_dev.argtypes = [ctypes.POINTER(ZnPatchBuildStridedItem), sz, vp]
         L.zn_copy_to_host.restype = ci; L.zn_copy_to_host.argtypes = [vp, vp, sz]
         L.zn_release_workspace.restype = ci
         L.zn_set_legacy_tree_descriptions.restype = ci
@@ -698,6 +713,41 @@ class ZnLib:
             for d, (sz_, st_) in enumerate(zip(sizes[:PATCH_MAX_DIMS], strides[:PATCH_MAX_DIMS])):
                 arr[i].size[d] = sz_; arr[i].stride[d] = st_
         self._check(self._L.zn_patch_apply_strided_batch_dev(arr, len(items), ctypes.c_void_p(stream or None), 1 if check else 0))
+
+    @staticmethod
+    def _patch_build_strided_items(items):
+        items = list(items)
+        arr = (ZnPatchBuildStridedItem * max(len(items), 1))()
+        for i, it in enumerate(items):
+            sp, bp, n, el, sizes, sstr, bstr = it[:7]
+            if len(sizes) != len(sstr) or len(sizes) != len(bstr):
+                raise ValueError("patch_build_strided: one stride per dimension on both sides")
+            arr[i].d_src = sp or None; arr[i].d_base = bp or None; arr[i].n = n; arr[i].elem = el; arr[i].ndim = len(sizes)
+            for d, (sz_, ss_, bs_) in enumerate(zip(sizes[:PATCH_MAX_DIMS], sstr[:PATCH_MAX_DIMS], bstr[:PATCH_MAX_DIMS])):
+                arr[i].size[d] = sz_; arr[i].src_stride[d] = ss_; arr[i].base_stride[d] = bs_
+            if len(it) > 7:
+                arr[i].d_patch = it[7] or None; arr[i].patch_cap = it[8]
+        return arr, len(items)
+
+    def patch_size_strided_batch_dev(self, items, stream=0):
+        """zn_patch_size_strided_batch_dev.  items: iterable of (src_ptr, base_ptr, n, elem, sizes, src_strides, base_strides): a source and a base that are strided
+        views over one logical shape (the pointers: where LOGICAL element 0 lies; strides in elements) -> the patches' lengths (0: the bytes are the base's)."""
+        arr, n = self._patch_build_strided_items(items)
+        out = (ctypes.c_size_t * max(n, 1))()
+        self._check(self._L.zn_patch_size_strided_batch_dev(arr, n, out, ctypes.c_void_p(stream or None)))
+        return [int(out[i]) for i in range(n)]
+
+    def patch_build_strided_batch_dev(self, items, stream=0):
+        """zn_patch_build_strided_batch_dev.  items: as for the size call, then (patch_ptr, patch_cap) -> the patches' lengths (0: identical, nothing written).
+        A short capacity raises ZnError(ZN_E_CAP) whose `needed` holds every item's length."""
+        arr, n = self._patch_build_strided_items(items)
+        rc = self._L.zn_patch_build_strided_batch_dev(arr, n, ctypes.c_void_p(stream or None))
+        if rc == ZN_E_CAP:
+            err = ZnError(rc, "patch_build_strided: a capacity is short")
+            err.needed = [int(arr[i].patch_len) for i in range(n)]
+            raise err
+        self._check(rc)
+        return [int(arr[i].patch_len) for i in range(n)]
 
     def patch_plan_create(self, items):
         """zn_patch_plan_create over items as for patch_apply_batch_dev -> an opaque handle (patch_plan_run / patch_plan_destroy)."""

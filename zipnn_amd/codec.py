@@ -301,16 +301,71 @@ def patch_build_device_batch(lib, pairs, sizes=None):
     return [arena[off:off + n] if n else None for off, n in zip(offs, lens)]
 
 
+def _patch_strided_pairs(pairs):
+    """[(source view, base view)] -> the items of ZnLib.patch_size_strided_batch_dev: two tensors of one dtype and shape on one device, each in a layout of its own."""
+    from . import _capi
+    items = []
+    for s, b in pairs:
+        if s.dtype != b.dtype or tuple(s.shape) != tuple(b.shape) or s.device != b.device or patch_elem(s) is None:
+            raise ValueError("patch: two tensors of the same dtype (1, 2 or 4 bytes per element) and shape on one device, fewer than 2^32 elements")
+        if s.dim() > _capi.PATCH_MAX_DIMS:
+            raise ValueError(f"patch: {s.dim()} dimensions (at most {_capi.PATCH_MAX_DIMS})")
+        m, el = s.numel(), s.element_size()
+        items.append((s.data_ptr() if m else 0, b.data_ptr() if m else 0, m * el, el, tuple(s.shape), tuple(s.stride()), tuple(b.stride())))
+    return items
+
+
+def patch_sizes_strided_device_batch(lib, pairs):
+    """pairs: [(source, base)]: tensors in any layouts zn_patch_size_strided_batch_dev accepts (include/zipnn_hip.h) -> the lengths of their
+    patches (0: identical bytes): the count pass alone, one read-back, no copy of either side."""
+    pairs = [(s.detach(), b.detach()) for s, b in pairs]
+    if not pairs:
+        return []
+    dev = pairs[0][0].device
+    with _device_of(dev):
+        return lib.patch_size_strided_batch_dev(_patch_strided_pairs(pairs), _stream_handle(pairs[0][0]))
+
+
+def patch_build_strided_device_batch(lib, pairs, sizes=None, return_arena=False):
+    """pairs: [(source, base)] as for patch_sizes_strided_device_batch -> their patches: uint8 tensors (views of one allocation, each at a multiple of 256
+    bytes), None where the bytes are identical — by ONE zn_patch_build_strided_batch_dev call, byte for byte what patch_build_device_batch gives for contiguous
+    copies of the views.  sizes: the lengths patch_sizes_strided_device_batch gave for the same pairs (else they are counted here).  return_arena: -> (the
+    patches, the allocation they are views of, or None)."""
+    pairs = [(s.detach(), b.detach()) for s, b in pairs]
+    if not pairs:
+        return ([], None) if return_arena else []
+    items = _patch_strided_pairs(pairs)
+    dev = pairs[0][0].device
+    if sizes is None:
+        with _device_of(dev):
+            sizes = lib.patch_size_strided_batch_dev(items, _stream_handle(pairs[0][0]))
+    offs, o = [], 0
+    for n in sizes:
+        offs.append(o)
+        o += (n + 255) // 256 * 256
+    arena = torch.empty(max(o, 16), dtype=torch.uint8, device=dev)
+    with _device_of(dev):
+        lens = lib.patch_build_strided_batch_dev([it + (arena.data_ptr() + off, n) for it, off, n in zip(items, offs, sizes)], _stream_handle(arena))
+    out = [arena[off:off + n] if n else None for off, n in zip(offs, lens)]
+    return (out, arena) if return_arena else out
+
+
 def patch_build(t, base):
     """The "znp1" patch (include/zipnn_hip.h) that turns `base` into `t`: the elements whose bytes differ, with their XOR values — a uint8 tensor on the
-    tensors' device, or None when the bytes are identical.  t and base: the same dtype (1, 2 or 4 bytes per element) and shape, on one device."""
+    tensors' device, or None when the bytes are identical.  t and base: the same dtype (1, 2 or 4 bytes per element) and shape, on one device.  Either may be
+    any strided view of at most 8 dimensions — a weight an engine keeps transposed, a column slice of a fused buffer, an expand()ed tensor —: both are read
+    where they lie, through their layouts (zn_patch_build_strided_batch_dev), and no contiguous copy is made; the patch is the one their
+    contiguous copies would give.  With p = patch_build(new, live.t()), patch_apply_(live.t(), p) leaves `new` in the live weight."""
     from . import _capi
     if t.dtype != base.dtype or tuple(t.shape) != tuple(base.shape) or t.device != base.device:
         raise ValueError("patch_build: two tensors of the same dtype and shape on one device")
     el = patch_elem(t)
     if el is None:
         raise ValueError(f"patch_build: {t.dtype} with {t.numel()} elements is not eligible (elements of 1, 2 or 4 bytes, fewer than 2^32 of them)")
-    return patch_build_device_batch(_capi.lib(), [(flat_bytes(t.detach()), flat_bytes(base.detach()), el)])[0]
+    t, base = t.detach(), base.detach()
+    if t.is_contiguous() and base.is_contiguous():
+        return patch_build_device_batch(_capi.lib(), [(flat_bytes(t), flat_bytes(base), el)])[0]
+    return patch_build_strided_device_batch(_capi.lib(), [(t, base)])[0]
 
 
 def patch_layout_refusal(t):

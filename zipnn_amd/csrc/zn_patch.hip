@@ -400,8 +400,8 @@ int patch_apply_launch(const PatchSet<S>& A, const S* d_table, hipStream_t strea
   return ZN_OK;
 }
 
-// One item of the strided call -> its segment, the layout CANONICAL: dimensions of size 1 dropped, neighbours merged where stride[i] == size[i + 1] stride[i + 1]
-// (a contiguous tensor becomes one dimension of stride 1, a single element none).  What remains must be INJECTIVE by the sufficient test: sorted by stride,
+// One item of the strided call -> its segment, the layout CANONICAL (zn_patch_layout_canon: dimensions of size 1 dropped, neighbours merged where
+// stride[i] == size[i + 1] stride[i + 1]; a contiguous tensor becomes one dimension of stride 1, a single element none).  What remains must be INJECTIVE by the sufficient test: sorted by stride,
 // every stride exceeds the sum over the smaller ones of (size - 1) stride — each dimension steps past everything the smaller ones span —, and no stride is 0.
 // That refuses expand() and overlapping as_strided views, and some injective layouts too (interleaved ones).  The largest offset stays below 2^62 elements.
 int patch_strided_segment(const zn_patch_apply_strided_item& it, ZnPatchLSeg& sg, bool& contiguous) {
@@ -423,13 +423,8 @@ int patch_strided_segment(const zn_patch_apply_strided_item& it, ZnPatchLSeg& sg
   contiguous = true;
   if (m == 0) return ZN_OK;                      // (no element, no workgroup: nothing is written)
   if (reach >> 62) return ZN_E_ARG;
-  uint32_t k = 0;
-  for (int d = 0; d < it.ndim; d++) {
-    const uint64_t sz = it.size[d], st = (uint64_t)it.stride[d];      // (sz <= m < 2^32; sz st <= 2 reach)
-    if (sz == 1u) continue;
-    if (k && sg.stride[k - 1u] == sz * st) { sg.size[k - 1u] *= (uint32_t)sz; sg.stride[k - 1u] = st; }
-    else { sg.size[k] = (uint32_t)sz; sg.stride[k] = st; k++; }
-  }
+  uint64_t none[ZN_PATCH_LAYOUT_DIMS];
+  const uint32_t k = zn_patch_layout_canon(it.ndim, it.size, it.stride, nullptr, sg.size, sg.stride, none);      // (every size <= m < 2^32; size stride <= 2 reach)
   sg.ndim = k;
   uint32_t order[ZN_PATCH_LAYOUT_DIMS];
   for (uint32_t i = 0; i < k; i++) order[i] = i;
@@ -442,6 +437,74 @@ int patch_strided_segment(const zn_patch_apply_strided_item& it, ZnPatchLSeg& sg
   }
   contiguous = k == 0 || (k == 1u && sg.stride[0] == 1u);
   return ZN_OK;
+}
+
+// The strided build: the checks of one side of an item — its strides over the item's sizes — -> the offset of its last element, in elements.
+// false: a negative stride, or a last element 2^62 elements or more away.
+bool patch_view_reach(const zn_patch_build_strided_item& it, const long long* stride, uint64_t& reach_out) {
+  unsigned __int128 reach = 0;
+  for (int d = 0; d < it.ndim; d++) {
+    if (stride[d] < 0) return false;
+    if (it.size[d]) reach += (unsigned __int128)(it.size[d] - 1u) * (uint64_t)stride[d];
+  }
+  if (it.n && (reach >> 62)) return false;
+  reach_out = it.n ? (uint64_t)reach : 0u;
+  return true;
+}
+
+// The sizes of the patches of strided sources against strided bases; with `emit`: … and the patches (patch_build's counterpart).  Sources are only read: a
+// stride of 0 and overlapping views are accepted.  A batch whose items all collapse to contiguous tensors on both sides takes patch_build's launches.
+int patch_build_strided(const zn_patch_build_strided_item* items, size_t count, std::vector<uint64_t>& lens, bool emit, hipStream_t stream) {
+  lens.assign(count, 0);
+  if (count == 0) return ZN_OK;
+  if (count > 0x7FFFFFFFull) return ZN_E_ARG;
+  std::vector<ZnPatchGSeg> segs(count);
+  std::vector<ZnPatchBSeg> scan(count);
+  std::vector<size_t> caps(count);
+  uint64_t wg = 0, words = 0;
+  bool all_contiguous = true;
+  for (size_t i = 0; i < count; i++) {
+    const zn_patch_build_strided_item& it = items[i];
+    if (it.ndim < 0 || it.ndim > (int)ZN_PATCH_LAYOUT_DIMS || !zn_patch_elem_ok(it.n, it.elem)) return ZN_E_ARG;
+    const uint64_t m = it.n / (size_t)it.elem;
+    uint64_t prod = 1, sreach, breach;
+    for (int d = 0; d < it.ndim; d++) {
+      const uint64_t sz = it.size[d];
+      if (prod && sz && prod > ~0ull / sz) return ZN_E_ARG;
+      prod *= sz;
+    }
+    if (prod != m) return ZN_E_ARG;
+    if (!patch_view_reach(it, it.src_stride, sreach) || !patch_view_reach(it, it.base_stride, breach)) return ZN_E_ARG;
+    if (it.n && (!it.d_src || !it.d_base || !patch_aligned(it.d_src, it.elem) || !patch_aligned(it.d_base, it.elem))) return ZN_E_ARG;
+    if (emit && it.patch_cap) {
+      if (!zn_patch_out_ok(it.d_patch)) return ZN_E_ARG;
+      if (it.n && (zn_patch_overlap(it.d_patch, it.patch_cap, it.d_src, (size_t)(sreach + 1u) * (size_t)it.elem) ||
+                   zn_patch_overlap(it.d_patch, it.patch_cap, it.d_base, (size_t)(breach + 1u) * (size_t)it.elem))) return ZN_E_ARG;
+    }
+    ZnPatchGSeg& sg = segs[i];
+    sg = ZnPatchGSeg{(const uint8_t*)it.d_src, (const uint8_t*)it.d_base, (uint8_t*)it.d_patch, m, {}, {}, {}, (uint32_t)wg, (uint32_t)words, (uint32_t)it.elem, 0u, 0u, 0u};
+    if (m) {                                     // (every size is in 1 .. m < 2^32)
+      sg.ndim = zn_patch_layout_canon(it.ndim, it.size, it.src_stride, it.base_stride, sg.size, sg.sstride, sg.bstride);
+      for (uint32_t d = 0; d < sg.ndim; d++) {   // the dimension memory is followed along: the smallest non-zero source stride, ties by the base's
+        const uint64_t ks = sg.sstride[d] ? sg.sstride[d] : ~0ull, kb = sg.bstride[d] ? sg.bstride[d] : ~0ull;
+        const uint64_t fs = sg.sstride[sg.fast] ? sg.sstride[sg.fast] : ~0ull, fb = sg.bstride[sg.fast] ? sg.bstride[sg.fast] : ~0ull;
+        if (ks < fs || (ks == fs && kb < fb)) sg.fast = d;
+      }
+      all_contiguous = all_contiguous && (sg.ndim == 0 || (sg.ndim == 1u && sg.sstride[0] == 1u && sg.bstride[0] == 1u));
+    }
+    scan[i] = ZnPatchBSeg{nullptr, nullptr, nullptr, m, 0u, (uint32_t)words, (uint32_t)it.elem, 0u};
+    caps[i] = it.patch_cap;
+    wg += zn_patch_blocks(m); words += zn_patch_blocks(m) + 1u;
+    if (wg > 0x7FFFFFFFull || words > 0x7FFFFFFFull) return ZN_E_ARG;
+  }
+  if (all_contiguous) {                          // every layout collapsed to the tensor itself: the contiguous launches
+    std::vector<PatchSrc> plain(count);
+    for (size_t i = 0; i < count; i++) plain[i] = PatchSrc{items[i].d_src, items[i].d_base, items[i].n, items[i].elem, items[i].d_patch, items[i].patch_cap};
+    return patch_build(plain, lens, emit, stream);
+  }
+  return zn_patch_two_pass(segs, scan.data(), wg, words, emit ? caps.data() : nullptr, lens, stream,
+                           [](const ZnPatchGSeg& one, const ZnPatchGSeg* d, uint32_t n, uint32_t g, uint32_t* wd, uint32_t*, hipStream_t st) { zn_launch_patch_count_strided(one, d, n, g, wd, st); },
+                           [](const ZnPatchGSeg& one, const ZnPatchGSeg* d, uint32_t n, uint32_t g, uint32_t* wd, uint32_t*, hipStream_t st) { zn_launch_patch_emit_strided(one, d, n, g, wd, st); });
 }
 
 }  // namespace
@@ -524,6 +587,30 @@ int zn_patch_apply_strided_batch_dev(const zn_patch_apply_strided_item* items, s
     PatchApplySet P;
     const int rc = patch_apply_segments(plain.data(), count, P);
     return rc ? rc : patch_apply_launch<ZnPatchASeg>(P, nullptr, (hipStream_t)stream_, check);
+  } catch (...) { return ZN_E_ALLOC; }
+}
+
+int zn_patch_size_strided_batch_dev(const zn_patch_build_strided_item* items, size_t count, size_t* sizes_out, void* stream_) {
+  try {
+    if (count == 0) return ZN_OK;
+    if (!items || !sizes_out) return ZN_E_ARG;
+    std::vector<uint64_t> lens;
+    const int rc = patch_build_strided(items, count, lens, false, (hipStream_t)stream_);
+    if (rc) return rc;
+    for (size_t i = 0; i < count; i++) sizes_out[i] = (size_t)lens[i];
+    return ZN_OK;
+  } catch (...) { return ZN_E_ALLOC; }
+}
+
+int zn_patch_build_strided_batch_dev(zn_patch_build_strided_item* items, size_t count, void* stream_) {
+  try {
+    if (count == 0) return ZN_OK;
+    if (!items) return ZN_E_ARG;
+    for (size_t i = 0; i < count; i++) items[i].patch_len = 0;
+    std::vector<uint64_t> lens;
+    const int rc = patch_build_strided(items, count, lens, true, (hipStream_t)stream_);
+    if (rc == ZN_OK || rc == ZN_E_CAP) for (size_t i = 0; i < count; i++) items[i].patch_len = (size_t)lens[i];      // (ZN_E_CAP: the lengths that were needed; nothing was written)
+    return rc;
   } catch (...) { return ZN_E_ALLOC; }
 }
 

@@ -69,6 +69,36 @@ __host__ __device__ static inline uint64_t zn_patch_layout_offset(uint32_t ndim,
 // has collapsed it (ndim <= 8 dimensions, no size 1, no stride 0, injective; the sizes' product is n / E); its first workgroup — one per block of the tensor.
 struct ZnPatchLSeg { const uint8_t* patch; uint64_t patch_len; uint64_t n; uint8_t* dst; uint64_t stride[ZN_PATCH_LAYOUT_DIMS]; uint32_t size[ZN_PATCH_LAYOUT_DIMS]; uint32_t wg0; uint32_t E; uint32_t ndim; uint32_t pad_; };
 void zn_launch_patch_apply_strided(const ZnPatchLSeg& one, const ZnPatchLSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_status, hipStream_t stream);
+// Two layouts over ONE logical shape made canonical together (the strided apply has one: sb == nullptr): dimensions of size 1 dropped, neighbours merged where
+// stride[i] == size[i + 1] stride[i + 1] in BOTH lists.  The caller has checked: ndim <= 8, no stride negative, every size in 1 .. 2^32 - 1.  -> the number of
+// dimensions left (a contiguous tensor: one, of stride 1; a single element: none).  Touches no memory.
+static inline uint32_t zn_patch_layout_canon(int ndim, const unsigned long long* size, const long long* sa, const long long* sb, uint32_t (&osize)[ZN_PATCH_LAYOUT_DIMS],
+                                             uint64_t (&osa)[ZN_PATCH_LAYOUT_DIMS], uint64_t (&osb)[ZN_PATCH_LAYOUT_DIMS]) {
+  uint32_t k = 0;
+  for (int d = 0; d < ndim; d++) {
+    const uint64_t sz = size[d], a = (uint64_t)sa[d], b = sb ? (uint64_t)sb[d] : 0u;
+    if (sz == 1u) continue;
+    if (k && osa[k - 1u] == sz * a && (!sb || osb[k - 1u] == sz * b)) { osize[k - 1u] *= (uint32_t)sz; osa[k - 1u] = a; osb[k - 1u] = b; }
+    else { osize[k] = (uint32_t)sz; osa[k] = a; osb[k] = b; k++; }
+  }
+  return k;
+}
+// ---- a patch built from strided sources : zn_patch_strided.hip ----
+// One item of a strided count / emit launch: ZnPatchBSeg's fields, the logical shape as the host has made it canonical jointly for both sides (ndim <= 8, no
+// size 1; a stride may be 0: sources are only read) with the source's and the base's strides over it, and `fast`: the dimension along which memory is followed
+// (the smallest non-zero source stride, ties by the base's).  src / base: where LOGICAL element 0 of each lies.
+struct ZnPatchGSeg {
+  const uint8_t* src; const uint8_t* base; uint8_t* patch; uint64_t m;
+  uint64_t sstride[ZN_PATCH_LAYOUT_DIMS], bstride[ZN_PATCH_LAYOUT_DIMS]; uint32_t size[ZN_PATCH_LAYOUT_DIMS];
+  uint32_t wg0; uint32_t w0; uint32_t E; uint32_t ndim; uint32_t fast; uint32_t pad_;
+};
+void zn_launch_patch_count_strided(const ZnPatchGSeg& one, const ZnPatchGSeg* d_segs, uint32_t nseg, uint32_t total_wg, uint32_t* d_words, hipStream_t stream);
+void zn_launch_patch_emit_strided(const ZnPatchGSeg& one, const ZnPatchGSeg* d_segs, uint32_t nseg, uint32_t total_wg, const uint32_t* d_words, hipStream_t stream);
+// What zn_patch_two_pass (zn_patch_host.hpp) asks of a segment type.  reads_patches: its inputs are patches, which may be malformed — the passes get a verdict
+// word.  The builds read tensors: none.
+template <typename S> struct ZnPatchSegTraits { static constexpr bool reads_patches = true; };
+template <> struct ZnPatchSegTraits<ZnPatchBSeg> { static constexpr bool reads_patches = false; };
+template <> struct ZnPatchSegTraits<ZnPatchGSeg> { static constexpr bool reads_patches = false; };
 
 #if defined(__HIPCC__) || defined(ZN_SIMT_EMULATOR)
 template <uint32_t E> struct ZnPatchElem;
@@ -97,6 +127,28 @@ __device__ __forceinline__ void zn_patch_wave_sums(const uint32_t* part, uint32_
   before = 0; all = 0;
 #pragma unroll
   for (uint32_t w = 0; w < ZN_PATCH_WAVES; w++) { const uint32_t q = part[w]; if (w < wave) before += q; all += q; }
+}
+
+// A block's 65 536 possible offsets as a bitmap in LDS (the merge; the strided build, §3.16): 2 048 words, 8 per thread of a prefix pass
+#define ZN_PM_WORDS (ZN_PATCH_BLOCK / 32u)
+#define ZN_PM_PER (ZN_PM_WORDS / ZN_PATCH_THREADS)      // bitmap words per thread of a prefix pass
+// pref[w] = the set bits of bm[0 .. w) -> the set bits of the whole bitmap.  Every thread of the workgroup; the bitmap is complete and visible on entry, pref
+// is on return.
+__device__ __forceinline__ uint32_t zn_pm_prefix(const uint32_t* bm, uint16_t* pref, uint32_t* part) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  uint32_t c[ZN_PM_PER], sum = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < ZN_PM_PER; k++) { c[k] = (uint32_t)__popc(bm[tid * ZN_PM_PER + k]); sum += c[k]; }
+  const uint32_t incl = zn_patch_wave_incl(sum, lane);
+  if (lane == 63u) part[wave] = incl;
+  __syncthreads();
+  uint32_t before, all;
+  zn_patch_wave_sums(part, wave, before, all);
+  uint32_t run = before + incl - sum;
+#pragma unroll
+  for (uint32_t k = 0; k < ZN_PM_PER; k++) { pref[tid * ZN_PM_PER + k] = (uint16_t)run; run += c[k]; }      // (run <= 65 504 at a word's start)
+  __syncthreads();
+  return all;
 }
 
 // The 32 header bytes as they lie there.  (zn_k_patch_check reads them itself: to it E is the byte at offset 4, and the three above it are padding with a finding of its own.)

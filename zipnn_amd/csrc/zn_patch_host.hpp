@@ -27,13 +27,14 @@ static inline int zn_patch_stage(Workspace& w, const void* table, size_t bytes, 
 // call): capacity check, then the emit pass for the items that keep entries.  Synchronous.  lens[i] = the length of item i's output, 0 where it has no entry.
 //   segs    the operation's items, wg0 / w0 filled for the count grid of `wg` workgroups over `words` scratch words; the driver renumbers wg0 for the emit grid
 //   scan    zn_k_patch_scan's view of the same items: the OUTPUT's m and E, and w0.  The build's items are that view themselves (S = ZnPatchBSeg, scan =
-//           segs.data()): one table serves count and scan.  The others read patches, which may be malformed: a table of their own for the scan, and a verdict
-//           word behind the totals that both passes may raise (ZN_E_CORRUPT; after the count pass before any capacity is looked at).
+//           segs.data()): one table serves count and scan.  Every other segment type has a table of its own for the scan.  Those that read patches, which may
+//           be malformed (ZnPatchSegTraits<S>::reads_patches), also have a verdict word behind the totals that both passes may raise (ZN_E_CORRUPT; after the
+//           count pass before any capacity is looked at); the strided build reads tensors and has none (its launchers receive a null d_status).
 //   launch_count / launch_emit (one, d_segs, nseg, total_wg, d_words, d_status, stream)
 template <typename S, typename Count, typename Emit>
 int zn_patch_two_pass(std::vector<S>& segs, const ZnPatchBSeg* scan, uint64_t wg, uint64_t words, const size_t* caps, std::vector<uint64_t>& lens, hipStream_t stream,
                       Count launch_count, Emit launch_emit) {
-  constexpr bool reads = !std::is_same<S, ZnPatchBSeg>::value;
+  constexpr bool reads = ZnPatchSegTraits<S>::reads_patches, own_scan = !std::is_same<S, ZnPatchBSeg>::value;
   const size_t count = segs.size();
   WsLease L;
   if (L.rc) return L.rc;
@@ -41,7 +42,7 @@ int zn_patch_two_pass(std::vector<S>& segs, const ZnPatchBSeg* scan, uint64_t wg
   t_kernels.clear();
   int rc;
   const bool table = count > 1;
-  const size_t seg_bytes = table ? count * sizeof(S) : 0u, scan_bytes = table && reads ? count * sizeof(ZnPatchBSeg) : 0u;
+  const size_t seg_bytes = table ? count * sizeof(S) : 0u, scan_bytes = table && own_scan ? count * sizeof(ZnPatchBSeg) : 0u;
   const size_t table_bytes = 2u * seg_bytes + scan_bytes;                        // count table, scan table, emit table (the emit pass has a grid of its own)
   const size_t back_bytes = (count + (reads ? 1u : 0u)) * sizeof(uint64_t);      // every item's T, and the verdict word behind them
   if ((rc = w.reserve(WS_META_A, words * sizeof(uint32_t)))) return rc;
@@ -58,11 +59,11 @@ int zn_patch_two_pass(std::vector<S>& segs, const ZnPatchBSeg* scan, uint64_t wg
     ZN_HIP(hipEventSynchronize(w.busy));         // the previous batched call may still be reading the pinned staging
     if ((rc = w.h_segs.reserve(table_bytes))) return rc;
     if ((rc = zn_patch_stage(w, segs.data(), seg_bytes, 0, stream))) return rc;
-    if (reads && (rc = zn_patch_stage(w, scan, scan_bytes, seg_bytes, stream))) return rc;
+    if (own_scan && (rc = zn_patch_stage(w, scan, scan_bytes, seg_bytes, stream))) return rc;
   }
   const uint8_t* d_tab = (const uint8_t*)w.buf[WS_SEGS];
   launch_count(segs[0], table ? (const S*)d_tab : nullptr, (uint32_t)count, (uint32_t)wg, d_words, d_status, stream);
-  zn_launch_patch_scan(scan[0], table ? (const ZnPatchBSeg*)(d_tab + (reads ? seg_bytes : 0u)) : nullptr, (uint32_t)count, d_words, d_totals, stream);
+  zn_launch_patch_scan(scan[0], table ? (const ZnPatchBSeg*)(d_tab + (own_scan ? seg_bytes : 0u)) : nullptr, (uint32_t)count, d_words, d_totals, stream);
   if (launch_failed()) return ZN_E_HIP;
   ZN_HIP(hipMemcpyAsync(w.h_totals.p, d_totals, back_bytes, hipMemcpyDeviceToHost, stream));
   ZN_HIP(hipStreamSynchronize(stream));

@@ -15,9 +15,6 @@
 // if an input changed between the two passes the result is wrong, not the memory around it.
 #include "zn_patch_host.hpp"
 
-#define ZN_PM_WORDS (ZN_PATCH_BLOCK / 32u)
-#define ZN_PM_PER (ZN_PM_WORDS / ZN_PATCH_THREADS)      // bitmap words per thread of a prefix pass
-
 struct ZnPmLds {
   uint32_t bmA[ZN_PM_WORDS], bmB[ZN_PM_WORDS], keep[ZN_PM_WORDS];
   uint16_t prefB[ZN_PM_WORDS], prefK[ZN_PM_WORDS];
@@ -41,25 +38,6 @@ __device__ __forceinline__ bool zn_pm_open(const uint8_t* __restrict__ p, uint64
   if (zn_patch_pair_bad(f0, f1, total, b, nb) || f1 - f0 > left) return false;
   in.off = (const uint16_t*)(p + zn_patch_a1(nb)); in.val = (const T*)(p + zn_patch_a2(nb, total)); in.f0 = f0; in.f1 = f1;
   return true;
-}
-
-// pref[w] = the set bits of bm[0 .. w) -> the set bits of the whole bitmap.  Every thread of the workgroup; the bitmap is complete and visible on entry, pref
-// is on return.
-__device__ __forceinline__ uint32_t zn_pm_prefix(const uint32_t* bm, uint16_t* pref, uint32_t* part) {
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  uint32_t c[ZN_PM_PER], sum = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < ZN_PM_PER; k++) { c[k] = (uint32_t)__popc(bm[tid * ZN_PM_PER + k]); sum += c[k]; }
-  const uint32_t incl = zn_patch_wave_incl(sum, lane);
-  if (lane == 63u) part[wave] = incl;
-  __syncthreads();
-  uint32_t before, all;
-  zn_patch_wave_sums(part, wave, before, all);
-  uint32_t run = before + incl - sum;
-#pragma unroll
-  for (uint32_t k = 0; k < ZN_PM_PER; k++) { pref[tid * ZN_PM_PER + k] = (uint16_t)run; run += c[k]; }      // (run <= 65 504 at a word's start)
-  __syncthreads();
-  return all;
 }
 
 // entries of one input into its bitmap; -> something is wrong with them (an offset beyond the tensor's last element, not above its predecessor, or seen twice;

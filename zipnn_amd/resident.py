@@ -271,6 +271,8 @@ class ResidentCheckpoint:
 
         ft.apply_({"o_proj.weight": live.t(), "up_proj.weight": fused[:, a:b]})     # live tensors at any strides that pass the injectivity test; ft.patch(name) for other shapes
 
+        cap = ResidentCheckpoint.from_live({"o_proj.weight": live.t(), "up_proj.weight": fused[:, a:b]}, base)      # … and the way back: live weights captured as a variant store, patches built where they lie
+
     CONTENT DIGESTS ("zn64-1"; an error-detecting code, not a cryptographic hash) let a store answer whether what it decodes is still what it was built from:
 
         store = ResidentCheckpoint.from_state_dict(sd, "cuda:0", digests=True)       # or from_file(path, dev, digests=True, verify=True)
@@ -550,6 +552,81 @@ class ResidentCheckpoint:
         store._digests = recorded
         if index:
             store.build_index(deltas=(index == "deltas"))
+        return store
+
+    @classmethod
+    def from_live(cls, live, base, ratio=1 / 8, digests=False):
+        """CAPTURE live weights as a variant store over `base`: what a trainer or a policy update left in an engine's own layout, as the store
+        whose patches the other replicas apply.  live: a mapping of names to tensors, or a module — tensors on the base's device in any layout
+        zn_patch_build_strided_batch_dev accepts (transposed, a column slice of a fused buffer, a tile shuffle, at most 8 dimensions); base: whatever
+        from_state_dict(base=...) accepts.  The device is the tensors'.
+
+        Every tensor the base holds with the same dtype and shape, and whose elements a patch can describe, is COUNTED against its base where both lie — one
+        batched strided size call per group of at most 1 GiB of tensors; a resident base is decoded a group at a time —: identical bytes give a "same" entry;
+        a patch shorter than ratio x the tensor's bytes gives a sparse entry, built by one batched strided build call per group.  Such a tensor gets no plain
+        body, no delta body and no contiguous copy.  Everything else — integers, tensors without a counterpart, patches at or above the ratio — goes, as a
+        contiguous copy, through from_state_dict(..., base=base, sparse=True), and its entries are taken over.
+        ratio is a POLICY, not from_state_dict's smallest-of-three rule: a huff0-coded plane spends at least one bit per byte, so a patch below
+        1/8 of the tensor is below any delta body whose planes are all coded — but a tensor that is constant apart from a few elements can have a smaller plain
+        body, which this constructor never looks for.
+        The result is an ordinary variant store that keeps `base` alive: get_tensor(s), get_slice, plan, hook, verify, apply_ / revert_,
+        save_file(sparse=True), rebased and sharded work on it.  digests=True: the sources are digested as from_state_dict does; a non-contiguous one
+        goes through a contiguous copy, as in holds() — a group's at a time, so the copies alive at once are bounded by the same 1 GiB (or one larger tensor),
+        but with digests the capture is no longer free of tensor-sized scratch."""
+        live = {name: t.detach() for name, t in _named_tensors(live).items()}
+        if not live:
+            raise ValueError("from_live: no tensors")
+        dev = next(iter(live.values())).device
+        if any(t.device != dev for t in live.values()):
+            raise ValueError("from_live: tensors on one device")
+        lib = _capi.lib()
+        based = cls._base_items(base, dev)
+        coders, prms, heads, cand = {}, {}, {}, []
+        for name, t in live.items():
+            ref = based.get(name)
+            if (ref is None or not ref.fits(t.dtype, t.shape) or t.dim() > _capi.PATCH_MAX_DIMS or t.numel() == 0 or not torch.is_floating_point(t)
+                    or t.dtype == torch.float64 or dtype_from_user(t.dtype) is None):
+                continue
+            heads[name], prm = _frame_params_for(t.dtype, t.shape, None, coders)
+            if codec.patch_elem(t) == prm[0] and ref.decodes_under(prm, coders):
+                prms[name] = prm
+                cand.append(name)
+        recorded = {} if digests else None     # (filled a group at a time: a non-contiguous source is digested through a copy, and no more than a group's are alive at once)
+        entries, keep, held = {}, [], 0
+        with _device_of(dev):
+            for grp in _groups(cand, lambda name: live[name].numel() * live[name].element_size(), cls._BUILD_GROUP_BYTES):
+                via = [name for name in grp if based[name].tensor is None]
+                decoded = base.get_tensors(via) if via else {}
+                pairs = [(live[name], decoded[name] if based[name].tensor is None else based[name].tensor) for name in grp]
+                if digests:
+                    recorded.update(zip(grp, codec.digests_of(lib, [live[name] for name in grp])))
+                sizes = codec.patch_sizes_strided_device_batch(lib, pairs)
+                take = [k for k, name in enumerate(grp) if 0 < sizes[k] < ratio * live[name].numel() * live[name].element_size()]
+                built, arena = codec.patch_build_strided_device_batch(lib, [pairs[k] for k in take], [sizes[k] for k in take], return_arena=True)
+                for k, name in enumerate(grp):
+                    if sizes[k] == 0:
+                        entries[name] = _Entry.same(name, live[name].dtype, live[name].shape, based[name], prms[name], head=heads[name])
+                for k, p in zip(take, built):
+                    name = grp[k]
+                    entries[name] = _Entry.sparse(name, live[name].dtype, live[name].shape, based[name], prms[name], p, head=heads[name])
+                    held += _round_up(p.numel())
+                if built:
+                    keep.append(arena)         # the group's patches are views of it
+                del decoded, pairs
+        rest = {name: t.contiguous() for name, t in live.items() if name not in entries}
+        if rest:                               # the chooser's entries, bodies and links are taken over as they are
+            if digests:                        # (of the contiguous copies the chooser takes anyway)
+                todo = [name for name in rest if name not in recorded]
+                recorded.update(zip(todo, codec.digests_of(lib, [rest[name] for name in todo])))
+            sub = cls.from_state_dict(rest, dev, base=base, sparse=True)
+            entries.update(sub._entries)
+            keep.extend(sub._keep)
+            held += sub._held
+        else:
+            keep.append(base)
+        cls._link_restore([entries[name] for name in cand if name in entries], based)
+        store = cls(dev, [entries[name] for name in live.keys()], held, keep=keep)
+        store._digests = {name: recorded[name] for name in live.keys()} if digests else None
         return store
 
     @classmethod
